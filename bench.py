@@ -18,6 +18,19 @@ protocol): the exact-f32 mode, the f16x2 mode (fp16 pairs: three MFMAs per produ
 64 / 128 / 256 and BASELINE config 2 (64x64x3, z=64, batch 128).  `comm` says what the gradient exchange ran on.
 `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py = the reference's torch-CPU algorithm) on this box's host cores: 2 warm-ups,
 best of 5, threads = min(affinity mask, cgroup CPU quota).
+
+A plain run measures the headline only: set-up, W warm-up steps (plus the untimed settle steps), exactly K timed steps of the
+uninstrumented step, one JSON line.  `--full` adds everything else, as described above: the roofline events (one instrumented step
+inside the timed region, serial schedule), the per-bucket `comm` trace on several ranks, `--tags-out`, the `variants` /
+`exact_f32` legs and `cpu_baseline`.
+
+`--dump-outputs DIR` writes, after the timed region, what the last timed step computed, as float32 .npy files: loss.npy,
+recon.npy, kl.npy (the step's return values), x_tilde.npy, mu.npy, logvar.npy, param.<name>.npy (every parameter after the
+update) and buffer.<name>.npy (BatchNorm running statistics).  An array larger than its cap is replaced by a fixed, seeded sample
+of its elements (sorted flat positions); the whole set stays under 64 MB.  Inputs and initial weights are seeded, so two builds
+run with the same arguments can be compared file for file, e.g.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_out/
 """
 import argparse
 import json
@@ -97,8 +110,17 @@ def parse():
     ap.add_argument("--dp-overlap", type=int, choices=[0, 1], default=1,
                     help="multi-GPU: 0 = ONE all-reduce of the whole gradient arena after backward")
     ap.add_argument("--no-settle", action="store_true", help="do exactly --warmup untimed steps (no power-state settling)")
-    ap.add_argument("--tags-out", type=str, default="", help="write per-layer conv timings (JSON) to this file")
-    return ap.parse_args()
+    ap.add_argument("--tags-out", type=str, default="", help="write per-layer conv timings (JSON) to this file (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline events, comm trace, variants, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.tags_out and not args.full:
+        ap.error("--tags-out needs --full (the per-layer timings come from the instrumented step)")
+    return args
 
 
 def cpu_baseline(args):
@@ -185,7 +207,7 @@ def build_step(B, S, C, z, precision, rank, graph=False):
     return fused, x, eps
 
 
-def measure(fused, x, eps, steps, untimed, world, graph, overlap=True, tags_out=""):
+def measure(fused, x, eps, steps, untimed, world, graph, overlap=True, tags_out="", instrument=True, snapshot=None):
     """`untimed` warm-up/settle steps, then EXACTLY `steps` timed steps between barrier + synchronize pairs.
     HIP events bracket the convolution launches of ONE timed step only (the middle one), with pre-created events: an event
     record is a barrier packet on the stream and 52 of them per step cost 0.4-2 ms of pipeline bubbles, which made the figure
@@ -193,10 +215,12 @@ def measure(fused, x, eps, steps, untimed, world, graph, overlap=True, tags_out=
     main stream instead of the side stream, optimiser at the end) so that an event pair times one kernel alone: it costs
     ~0.6 ms more than a plain step, i.e. +0.03 ms on the 20-step average (two instrumented steps, rounds 1-3: +0.06 ms = 1.7 % --
     the same binary over 1 500 steps measures 3.43 ms where the 20-step region with two of them measured 3.49); the other K-1
-    steps run the concurrent schedule."""
+    steps run the concurrent schedule.  ``instrument=False`` (a plain run of bench.py): no events, no instrumented step, all K
+    timed steps are the plain step.  ``snapshot(loss, recon, kl)`` is called once right after the timed region, before anything
+    else can overwrite the plan's output buffers; its result is returned as ``outputs``."""
     for _ in range(untimed):
         fused.step(x, eps, overlap=overlap)
-    timers = None if graph else {"names": CONV_CALLS, "events": [], "pool": {}, "slot": 0}
+    timers = None if (graph or not instrument) else {"names": CONV_CALLS, "events": [], "pool": {}, "slot": 0}
     N_INST = 1
     if timers is not None:    # create the events (hipEventCreate is not free) outside the timed region
         for sl in range(N_INST):
@@ -230,15 +254,16 @@ def measure(fused, x, eps, steps, untimed, world, graph, overlap=True, tags_out=
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = tmax.item()
     final_loss = loss.item()
-    measured = "timed-region"
-    if timers is None:  # graph replay cannot carry events: instrumented eager pass of the same K steps
+    outputs = snapshot(loss, recon, kl) if snapshot is not None else None
+    measured = "timed-region" if instrument else None
+    if timers is None and instrument:  # graph replay cannot carry events: instrumented eager pass of the same K steps
         timers = {"names": CONV_CALLS, "events": []}
         for _ in range(steps):
             fused.forward_backward(x, eps, timers)
         torch.cuda.synchronize()
         measured = "instrumented-pass-after-timed-region"
     fam = {}
-    for name, tag, flops, e0, e1 in timers["events"]:
+    for name, tag, flops, e0, e1 in (timers["events"] if timers is not None else []):
         d = fam.setdefault(name.replace("_stats_", "_").replace("_cus", ""), [0.0, 0.0, 0, 0.0])
         d[0] += flops
         d[1] += e0.elapsed_time(e1) * 1e-3
@@ -252,9 +277,53 @@ def measure(fused, x, eps, steps, untimed, world, graph, overlap=True, tags_out=
         with open(tags_out, "w") as f:
             json.dump({k: {"ms": round(v[1] / v[2] * 1e3, 4), "gflop": round(v[0] / v[2] / 1e9, 3),
                            "tflops": round(v[0] / v[1] / 1e12, 2)} for k, v in per.items()}, f, indent=1)
-    n_inst = len(inst) if measured == "timed-region" else steps
+    n_inst = len(inst) if measured == "timed-region" else steps if instrument else 0
     return {"elapsed": elapsed, "loss": final_loss, "fam": fam, "n_inst": n_inst, "measured": measured,
-            "comm_trace": trace.summary() if trace is not None else None}
+            "comm_trace": trace.summary() if trace is not None else None, "outputs": outputs}
+
+
+DUMP_CAP_OUTPUT = 1 << 22     # elements kept of x_tilde / mu / logvar (16 MB each at most)
+DUMP_CAP_PARAM = 1 << 17      # elements kept of one parameter or buffer (512 KB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _sample(t, cap, seed):
+    """``t`` flattened, whole when it has at most ``cap`` elements, else a fixed sample of ``cap`` of them: positions drawn without
+    replacement by a generator seeded with ``seed``, in increasing order."""
+    import numpy as np
+    flat = t.detach().reshape(-1)
+    if flat.numel() > cap:
+        pos = np.sort(np.random.default_rng(seed).choice(flat.numel(), cap, replace=False))
+        flat = flat[torch.from_numpy(pos).to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def output_snapshot(fused):
+    """What one call of ``fused.step`` hands its caller, copied to the host: the returned (loss, recon, kl), the plan's forward
+    outputs (x_tilde, mu, logvar) and the model state the step updated (parameters, BatchNorm running statistics).  Float32; an
+    array above its cap is a seeded sample (``_sample``), so the set is the same from run to run for the same arguments."""
+    def snap(loss, recon, kl):         # (called after the timed region's closing synchronize)
+        out = {"loss": loss, "recon": recon, "kl": kl}
+        out = {k: v.detach().float().cpu().numpy().reshape(()) for k, v in out.items()}
+        for i, (k, v) in enumerate((("x_tilde", fused.x_tilde), ("mu", fused.mu), ("logvar", fused.logvar))):
+            out[k] = (v.detach().float().cpu().numpy() if v.numel() <= DUMP_CAP_OUTPUT else _sample(v, DUMP_CAP_OUTPUT, 100 + i))
+        for i, (k, p) in enumerate(fused.vae.named_parameters()):
+            out["param." + k] = p.detach().float().cpu().numpy() if p.numel() <= DUMP_CAP_PARAM else _sample(p, DUMP_CAP_PARAM, 1000 + i)
+        for i, (k, b) in enumerate(fused.vae.named_buffers()):
+            if b.is_floating_point():
+                out["buffer." + k] = _sample(b, DUMP_CAP_PARAM, 2000 + i)
+        return out
+    return snap
+
+
+def write_outputs(outputs, out_dir):
+    import numpy as np
+    total = sum(a.nbytes for a in outputs.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in outputs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.asarray(a, dtype=np.float32))
 
 
 def roofline_of(m, steps, B, S, C, z):
@@ -347,7 +416,10 @@ def main():
     # The count is fixed (not time-based) so that every rank of a multi-GPU run executes the same collectives.
     n_settle = max(0, SETTLE_STEPS - args.warmup) if not args.no_settle else 0
     m = measure(fused, x, eps, args.steps, args.warmup + n_settle, world, args.graph, overlap=bool(args.dp_overlap),
-                tags_out=args.tags_out if rank == 0 else "")
+                tags_out=args.tags_out if rank == 0 else "", instrument=args.full,
+                snapshot=output_snapshot(fused) if args.dump_outputs and rank == 0 else None)
+    if m["outputs"] is not None:
+        write_outputs(m["outputs"], args.dump_outputs)
 
     out = None
     if rank == 0:
@@ -364,11 +436,11 @@ def main():
             "images_per_sec_per_gpu": round(ips / world, 1),
             "step_algorithmic_tflops_per_gpu": round(ips / world * STEP_GFLOP.get(S, 0.0) / 1e3, 1),
             "loss": round(m["loss"], 4),
-            "roofline": roofline_of(m, args.steps, B, S, C, z),
+            **({"roofline": roofline_of(m, args.steps, B, S, C, z)} if args.full else {}),
             "comm": comm_record(world, args, m.get("comm_trace")),
         }
     # ---- variants: one GPU only (their collectives would have to match on every rank), after the headline ----------------
-    if world == 1 and not args.no_variants:
+    if world == 1 and args.full and not args.no_variants:
         del fused
         torch.cuda.empty_cache()
         todo = []
@@ -406,7 +478,7 @@ def main():
                                     "dtype": "f32 (v_mfma_f32_32x32x2_f32 / 16x16x4: exact fp32 products, fp32 accumulate)"}
                 break
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,6 +1,6 @@
 """MFMA-busy share per kernel from one rocprofv3 PMC pass (serial schedule):
     VP_SIDE_WGRAD=0 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d D -o t -- \
-        python3 bench.py --steps 2 --warmup 1 --no-settle --no-cpu-baseline
+        python3 bench.py --full --steps 2 --warmup 1 --no-settle --no-cpu-baseline
 MFMA busy = SQ_VALU_MFMA_BUSY_CYCLES / (active cycles x 1024 SIMDs).  SQ_VALU_MFMA_BUSY_CYCLES counts shader cycles summed over
 all SIMDs (32 per v_mfma_f32_32x32x16_bf16: it reproduces the algorithmic count exactly, 157.29 M for a 53.69-GFLOP layer with
 three MFMAs per product); GRBM_GUI_ACTIVE comes back SUMMED over the 8 XCDs (17-18 G cycles per second of kernel time), so the

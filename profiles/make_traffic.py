@@ -1,5 +1,5 @@
 """HBM-side traffic per kernel from two rocprofv3 PMC passes (separate runs, as MI355X_MICROARCH.md prescribes):
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE  --output-format csv -d A -o t -- python3 bench.py --steps 2 --warmup 1 --no-settle --no-cpu-baseline
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE  --output-format csv -d A -o t -- python3 bench.py --full --steps 2 --warmup 1 --no-settle --no-cpu-baseline
     rocprofv3 --kernel-trace --pmc WRITE_SIZE  --output-format csv -d B -o t -- python3 bench.py ...   (VP_SIDE_WGRAD=0: serial schedule)
 usage: python profiles/make_traffic.py A/t_counter_collection.csv B/t_counter_collection.csv <steps incl. warm-up> <out.json> > out.md
 bytes = 2 * FETCH_SIZE * 1024 (gfx950 reports half of wide streaming reads) + WRITE_SIZE * 1024."""
@@ -27,7 +27,7 @@ F, W = load(fa), load(fb)
 fam = {"vp_conv5_gather_bf16x3": ("ProbF16", "PF16"), "vp_conv5_scatter_bf16x3": ("ProbT16", "PT16"),
        "vp_conv5_wgrad_bf16x3": ("ProbW16", "wgrad5_kernel")}
 res = {"_provenance": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE (separate passes, serial schedule VP_SIDE_WGRAD=0) of "
-       "`python bench.py --steps 2 --warmup 1 --no-settle --no-cpu-baseline` on one MI355X; bytes = 2*FETCH_SIZE*1024 (gfx950 reports "
+       "`python bench.py --full --steps 2 --warmup 1 --no-settle --no-cpu-baseline` on one MI355X; bytes = 2*FETCH_SIZE*1024 (gfx950 reports "
        "half of wide streaming reads, MI355X_MICROARCH.md HBM section) + WRITE_SIZE*1024, averaged over the launches of the igemm16 / "
        "igemm16p / wgrad5 kernels of each family (for the weight gradient: main kernel; its slab reduction is listed separately in the "
        ".md); "

@@ -45,7 +45,15 @@ def test_vaegan_oracle_matches_golden_step():
     p = G.init_vaegan_params(S, z, seed=0)
     O.require_grad(p)
     opts = G.make_optimizers(p)
-    out, losses = G.train_step(p, opts, x, targets, eps, z_p, S)
+    # the discriminator's net gradients are fp32 cancellation round-off (1e-6 of their terms, see test_gpu_vaegan._grad_check), so
+    # they -- and RMSprop's normalised first step on them -- follow the CPU summation order, which torch derives from its thread
+    # count: run the step with the 8 threads the fixture was written with, whatever the machine's CPU count
+    threads = torch.get_num_threads()
+    torch.set_num_threads(8)
+    try:
+        out, losses = G.train_step(p, opts, x, targets, eps, z_p, S)
+    finally:
+        torch.set_num_threads(threads)
     for k, v in out.items():
         if f"out/{k}" in g:
             assert torch.allclose(v, t(g[f"out/{k}"]), rtol=1e-5, atol=1e-6), k

@@ -7,9 +7,9 @@ O=$R/gpurun_out/prof
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
-B="bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-variants"
-P="bench.py --steps 2 --warmup 1 --no-settle --no-cpu-baseline --no-variants"
-timeout -k 10 500 python3 bench.py --tags-out $O/tags_bf16x3.json > $O/bench_default.json 2> $O/bench_default.err || exit 1
+B="bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-variants"
+P="bench.py --full --steps 2 --warmup 1 --no-settle --no-cpu-baseline --no-variants"
+timeout -k 10 500 python3 bench.py --full --tags-out $O/tags_bf16x3.json > $O/bench_default.json 2> $O/bench_default.err || exit 1
 echo "bench done"
 VP_SIDE_WGRAD=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_serial -o t -- python3 $B > $O/ks_serial.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks_conc -o t -- python3 $B > $O/ks_conc.log 2>&1 || exit 1

@@ -12,7 +12,7 @@ tail -n 6 $O/pytest.log
 echo "pytest rc=$rc"
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2> $O/smoke.err || exit 1
-timeout -k 10 400 python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1
+timeout -k 10 400 python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
 python3 - <<PY
 import json
 d = json.load(open("$O/bench.json"))

@@ -6,8 +6,8 @@ O=$R/gpurun_out/prof160
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 cd $R
-P="bench.py --steps 2 --warmup 1 --no-settle --no-cpu-baseline --no-variants"
+P="bench.py --full --steps 2 --warmup 1 --no-settle --no-cpu-baseline --no-variants"
 VP_SIDE_WGRAD=0 VP_WGRAD_MAIN_CUS=160 timeout -k 10 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/fetch -o t -- python3 $P > $O/fetch.log 2>&1 || exit 1
 VP_SIDE_WGRAD=0 VP_WGRAD_MAIN_CUS=160 timeout -k 10 300 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/write -o t -- python3 $P > $O/write.log 2>&1 || exit 1
-VP_SIDE_WGRAD=0 VP_WGRAD_MAIN_CUS=160 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o t -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-variants > $O/ks.log 2>&1 || exit 1
+VP_SIDE_WGRAD=0 VP_WGRAD_MAIN_CUS=160 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks -o t -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-variants > $O/ks.log 2>&1 || exit 1
 echo done

@@ -63,7 +63,8 @@ size_t vp_conv5_wgrad_workspace_bytes(int B, int Hs, int Ws, int Cbig, int Csmal
 int vp_conv5_wgrad_f32(const float* big, const float* small, float* dw_ref,
                        int B, int Hs, int Ws, int Cbig, int Csmall, int stride,
                        void* ws, size_t ws_bytes, vp_stream stream);
-/* As vp_conv5_wgrad_f32 with a bound on the CUs the launch occupies (see vp_conv5_wgrad_bf16x3_cus; max_cus <= 0: the whole chip). */
+/* As vp_conv5_wgrad_f32 with a bound on the CUs the launch occupies (see vp_conv5_wgrad_bf16x3_cus; max_cus <= 0: the whole chip;
+ * max_cus > 256, more than the chip has, behaves as 256).  Same workspace query as vp_conv5_wgrad_f32. */
 int vp_conv5_wgrad_f32_cus(const float* big, const float* small, float* dw_ref, int B, int Hs, int Ws, int Cbig, int Csmall,
                            int stride, int max_cus, void* ws, size_t ws_bytes, vp_stream stream);
 /* Exact-fp32 convolution + the statistics pass of the BatchNorm that follows it (models/networks.py:14-16,38-40) in one call, as
@@ -183,8 +184,8 @@ int vp_conv5_wgrad_bf16x3(const void* big_split, const void* small_split, float*
 /* The same with a bound on the CUs the launch occupies.  The row-of-taps kernel (csrc/wgrad5.h: one kernel row of 5 taps per
  * workgroup, replaces cuDNN's weight gradient behind models/networks.py:14,38) owns a whole CU per work item; a caller that runs the
  * weight gradient BESIDE other kernels -- the fused step's side stream -- leaves the rest of the chip to them (160 of 256 CUs is the
- * measured optimum there).  max_cus <= 0: the whole chip (= vp_conv5_wgrad_bf16x3).  Same workspace query, same result up to the
- * summation order of the pixel ranges. */
+ * measured optimum there).  max_cus <= 0: the whole chip (= vp_conv5_wgrad_bf16x3); max_cus > 256, more than the chip has, behaves
+ * as 256.  Same workspace query, same result up to the summation order of the pixel ranges. */
 int vp_conv5_wgrad_bf16x3_cus(const void* big_split, const void* small_split, float* dw_ref,
                               int B, int Hs, int Ws, int Cbig, int Csmall, int stride, int max_cus,
                               void* ws, size_t ws_bytes, vp_stream stream);

@@ -94,6 +94,7 @@ static int conv_wgrad_f32(const float* big, const float* small, float* dw_ref, i
   if (const int bn = wgrad5f_kind(g, big, small)) {
     int kper = 0, slabs = 0;
     const int ns5 = wgrad5_nsplit(g, bn, &kper, max_cus);
+    if (ws_bytes < wgrad5_slab_floats(g, bn, ns5) * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv_wgrad_f32: workspace too small");
     wgrad5f_launch(big, small, (float*)ws, g, bn, ns5, kper, (hipStream_t)stream, &slabs);
     rc = check_launch("vp_conv_wgrad_f32(rows of taps)");
     if (rc) return rc;

@@ -621,10 +621,13 @@ inline int wgrad5_bn(const ConvGeom& g) {
 // the measured optimum (step 3.588 ms with the one-tap kernels; rows of taps with 256 work items 3.52, 176: 3.479, 160: 3.455,
 // 144: 3.471, 128: 3.484, 96: 3.67 -- profiles/r03_notes.md): the main stream's kernels keep the rest instead of queueing behind
 // one-workgroup-per-CU launches, and the slabs shrink with the count.
+// A budget above the chip's WGRAD5_MAX_ITEMS CUs (MI355X: 256) means nothing more and is clamped to it: the workspace queries size
+// the slabs for items = 0, i.e. WGRAD5_MAX_ITEMS, so a larger count would split K deeper than the queried workspace holds.
+constexpr int WGRAD5_MAX_ITEMS = 256;
 inline int wgrad5_nsplit(const ConvGeom& g, int bn, int* k_per_split, int items = 0) {
   const long K = (long)g.B * g.Hs * g.Ws;
   const long inner = (long)(g.Cs / 128) * (g.Cb / bn) * 5;
-  long target = items > 0 ? items : 256;
+  long target = items > 0 && items < WGRAD5_MAX_ITEMS ? items : WGRAD5_MAX_ITEMS;
   if (const char* e = VP_GETENV("VP_WGRAD5_BLOCKS")) target = atol(e);       // A/B knob: overrides the caller's count
   long ns = target / inner;
   if (ns < 1) ns = 1;

@@ -436,6 +436,31 @@ int vp_conv5_scatter_stats_f16(const void* small_split, const void* w_p1_split, 
                                void* ws, size_t ws_bytes, vp_stream stream);
 
 
+/* ---- inference: eval-mode BatchNorm folded into the convolution's epilogue --------------------------------------------------
+ * In eval() a BatchNorm is the per-channel affine map y = s x + t with s = gamma / sqrt(running_var + eps) and
+ * t = beta - running_mean s (models/networks.py:16,28-29 and :40,44-45 under the eval() branch of VaeGan.forward,
+ * models/networks.py:248-258; the torch.no_grad() reconstruction of train.py:95-96).  vp_bn_fold_f32 writes s, t (and
+ * rstd = 1 / sqrt(running_var + eps) for the layers that keep vp_bn_act_fwd_f32) once per set of weights, formed in fp64 and rounded
+ * once; gamma / beta may be NULL (affine=False), each output may be NULL. */
+int vp_bn_fold_f32(const float* gamma, const float* beta, const float* running_mean, const float* running_var, float eps, float* scale,
+                   float* shift, float* rstd, int C, vp_stream stream);
+/* nn.Conv2d / nn.ConvTranspose2d (k5, p2, no bias) + eval-mode nn.BatchNorm2d + F.relu of a block in ONE launch (replaces
+ * models/networks.py:27-29 and :43-45 in eval mode): v = act(fma(acc, scale[n], shift[n])), act none | relu, written as fp32 NHWC
+ * (out_f32) and / or as the split planes of the next layer's operand (out_split, bf16x3 only: hi plane, then lo plane, the layout
+ * and rounding of vp_bn_act_fwd_split_f32); at least one output, 16-byte aligned.  The f32 entry points take out_split == NULL only.
+ * vp_conv5_affine_supported(family 0 gather | 1 scatter, precision 0 bf16x3 | 1 f32, ...) == 0: this launch shape does not fuse (its
+ * plain launch splits K, or its channel counts are outside the instantiated tiles: contracted side a multiple of 64 [f32: 32],
+ * output side >= 64 and a multiple of 8): use the plain entry point + vp_bn_act_fwd_split_f32. */
+int vp_conv5_affine_supported(int family, int precision, int B, int Hs, int Ws, int Cbig, int Csmall, int stride);
+int vp_conv5_gather_affine_bf16x3(const void* big_split, const void* w_p0_split, const float* scale, const float* shift, float* out_f32,
+                                  void* out_split, int B, int Hs, int Ws, int Cbig, int Csmall, int stride, int act, vp_stream stream);
+int vp_conv5_scatter_affine_bf16x3(const void* small_split, const void* w_p1_split, const float* scale, const float* shift, float* out_f32,
+                                   void* out_split, int B, int Hs, int Ws, int Csmall, int Cbig, int stride, int act, vp_stream stream);
+int vp_conv5_gather_affine_f32(const float* big, const float* w_p0, const float* scale, const float* shift, float* out_f32, void* out_split,
+                               int B, int Hs, int Ws, int Cbig, int Csmall, int stride, int act, vp_stream stream);
+int vp_conv5_scatter_affine_f32(const float* small, const float* w_p1, const float* scale, const float* shift, float* out_f32, void* out_split,
+                                int B, int Hs, int Ws, int Csmall, int Cbig, int stride, int act, vp_stream stream);
+
 /* ---- optimiser step on a flat arena (train_BE.py:62-64,131; train.py:136-140) --------------- */
 /* torch.optim.Adam semantics (no amsgrad, no weight decay); g is multiplied by grad_scale first
  * (1/world_size after a sum all-reduce). step is the 1-based step count. */

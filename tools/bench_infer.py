@@ -1,0 +1,196 @@
+#!/usr/bin/env python
+"""Inference benchmark: vae_play_amd.FusedVAEInference against the existing module path (``vae.eval()`` under ``torch.no_grad()``) in
+ONE process, on the same weights and inputs.
+
+For reconstruct, decode (= sample without the draw) and encode, at the benchmark shape (128x128x3, z = 128, batch 32) and at
+config 2 (64x64x3, z = 64, batch 128), in both precisions: ms per call and images/s of
+  modules      -- vae(x, eps) / vae.decoder(z) / vae.encoder(x), eval mode, no_grad, set_conv_precision(precision)
+  fused        -- the pre-planned launch list, eager
+  fused_graph  -- the same list replayed as a hipGraph
+Each figure is the median over ``--reps`` windows of ``--iters`` calls, a window bracketed by device events on the launch stream
+(so host-side gaps between launches are inside it: this is the time a caller waits, not kernel time); the variants alternate
+inside every repetition, and min / max over the repetitions are reported as the spread.  Every variant is warmed up first.
+
+``--layers`` adds, for every BatchNorm-followed 5x5 layer of the shape, the fused launch against convolution + normalise pass on
+preallocated buffers (the per-layer evidence for which form the plan keeps).  The result is one JSON document (``--out``).
+
+    python tools/bench_infer.py --out bench_out/infer.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+SHAPES = {"bench_128x128x3_z128_b32": (3, 128, 128, 32), "config2_64x64x3_z64_b128": (3, 64, 64, 128)}
+
+
+def window(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / iters
+
+
+def ab(variants, iters, reps, warmup):
+    """variants: {name: fn}; alternated inside each repetition.  -> {name: {"ms": median, "min", "max"}}"""
+    for fn in variants.values():
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    t = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, fn in variants.items():
+            t[k].append(window(fn, iters))
+    return {k: {"ms": statistics.median(v), "min": min(v), "max": max(v)} for k, v in t.items()}
+
+
+def randomise_bn(vae, seed):
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for m in vae.modules():
+            if hasattr(m, "num_batches_tracked"):
+                m.weight.copy_(torch.empty(m.weight.shape).uniform_(0.5, 1.5, generator=g))
+                m.bias.copy_(torch.randn(m.bias.shape, generator=g) * 0.2)
+                m.running_mean.copy_(torch.randn(m.bias.shape, generator=g) * 0.1)
+                m.running_var.copy_(torch.empty(m.bias.shape).uniform_(0.5, 2.0, generator=g))
+
+
+def bench_shape(name, C, S, z, B, prec, args):
+    import vae_play_amd as V
+    torch.manual_seed(0)
+    vae = V.VAE(S, z, C).cuda().eval()
+    randomise_bn(vae, 1)
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand((B, C, S, S), generator=g).cuda()
+    eps = torch.randn((B, z), generator=g).cuda()
+    zz = torch.randn((B, z), generator=g).cuda()
+    eager = V.FusedVAEInference(vae, B, S, C, precision=prec)
+    graph = V.FusedVAEInference(vae, B, S, C, precision=prec)
+    graph.capture()
+    V.set_conv_precision(prec)
+    out = {"fused_layers": eager.fused_layers, "unfused_layers": eager.unfused_layers}
+    try:
+        with torch.no_grad():
+            # the three paths compute the same thing (recorded, not asserted: the parity tests assert)
+            xm = vae(x, eps)[0]
+            out["max_abs_diff_fused_vs_modules_x_tilde"] = (eager.reconstruct(x, eps)[0] - xm).abs().max().item()
+            out["graph_equals_eager"] = bool(torch.equal(graph.reconstruct(x, eps)[0], eager.reconstruct(x, eps)[0]))
+            ops_ = {
+                "reconstruct": {"modules": lambda: vae(x, eps), "fused": lambda: eager.reconstruct(x, eps),
+                                "fused_graph": lambda: graph.reconstruct(x, eps)},
+                "decode": {"modules": lambda: vae.decoder(zz), "fused": lambda: eager.decode(zz), "fused_graph": lambda: graph.decode(zz)},
+                "encode": {"modules": lambda: vae.encoder(x), "fused": lambda: eager.encode(x), "fused_graph": lambda: graph.encode(x)},
+            }
+            for op, variants in ops_.items():
+                r = ab(variants, args.iters, args.reps, args.warmup)
+                for v in r.values():
+                    v["images_per_s"] = B / (v["ms"] * 1e-3)
+                r["saved_ms_fused_vs_modules"] = r["modules"]["ms"] - r["fused"]["ms"]
+                r["saved_ms_graph_vs_modules"] = r["modules"]["ms"] - r["fused_graph"]["ms"]
+                out[op] = r
+                print(f"{name} {prec} {op}: modules {r['modules']['ms']:.3f} ms [{r['modules']['min']:.3f}, {r['modules']['max']:.3f}]  "
+                      f"fused {r['fused']['ms']:.3f} [{r['fused']['min']:.3f}, {r['fused']['max']:.3f}]  "
+                      f"graph {r['fused_graph']['ms']:.3f} [{r['fused_graph']['min']:.3f}, {r['fused_graph']['max']:.3f}]", flush=True)
+    finally:
+        V.set_conv_precision("f32")
+    return out
+
+
+def bench_layers(C, S, z, B, prec, args):
+    """fused launch vs convolution + normalise pass, per BatchNorm-followed 5x5 layer, on preallocated buffers"""
+    import vae_play_amd as V
+    from vae_play_amd import _lib, ops
+    from ctypes import c_void_p
+    lib = _lib.load()
+    vae = V.VAE(S, z, C)
+    L = vae.iter_level
+    enc_ch = [C] + [blk.conv.weight.shape[0] for blk in vae.encoder.conv]
+    dec_ch = [vae.decoder._c0] + [blk.conv.weight.shape[1] for blk in list(vae.decoder.conv)[:L]]
+    layers = [(f"enc{i}", 0, S >> (i + 1), enc_ch[i], enc_ch[i + 1]) for i in range(1, L)]
+    layers += [(f"dec{i}", 1, 8 << i, dec_ch[i], dec_ch[i + 1]) for i in range(L)]
+    res = {}
+    P = lambda t: None if t is None else c_void_p(t.data_ptr())      # noqa: E731
+    for tag, fam, Hs, Cin, Cout in layers:
+        Cbig, Csmall = (Cin, Cout) if fam == 0 else (Cout, Cin)
+        if not ops.conv5_affine_supported(fam, prec, B, Hs, Hs, Cbig, Csmall, 2):
+            res[tag] = {"fused": None, "note": "launch shape not fusable (its plain launch splits K)"}
+            continue
+        Hin = 2 * Hs if fam == 0 else Hs
+        Ho = Hs if fam == 0 else 2 * Hs
+        a = torch.randn((B, Cin, Hin, Hin), device="cuda").contiguous(memory_format=torch.channels_last)
+        w = torch.randn((Cout, Cin, 5, 5) if fam == 0 else (Cin, Cout, 5, 5), device="cuda") / (25 * Cin) ** 0.5
+        n_out = B * Ho * Ho * Cout
+        last = tag == f"dec{L - 1}" or tag == f"enc{L - 1}" or prec == "f32"      # consumers that read fp32
+        y = torch.empty(n_out, device="cuda")
+        c = torch.empty(n_out, device="cuda")
+        ys = None if last else ops.empty_split(n_out, a)
+        ones, zeros = torch.ones(Cout, device="cuda"), torch.zeros(Cout, device="cuda")
+        s = torch.cuda.current_stream().cuda_stream
+        geom = (B, Hs, Hs, Cin, Cout, 2)
+        if prec == "bf16x3":
+            a_in, wp = ops.split_f32(a), ops.pack_w5_split(w, fam == 0, fam == 1)[fam]
+        else:
+            a_in, wp = a, ops.pack_w5(w, fam == 0, fam == 1)[fam]
+        fn_f = getattr(lib, ("vp_conv5_gather_affine_", "vp_conv5_scatter_affine_")[fam] + prec)
+        fn_c = getattr(lib, ("vp_conv5_gather_", "vp_conv5_scatter_")[fam] + prec)
+
+        def fused():
+            _lib.check(fn_f(P(a_in), P(wp), P(ones), P(zeros), None if ys is not None else P(y), P(ys), *geom, ops.ACT_RELU, c_void_p(s)))
+
+        def separate():
+            if fam == 0:
+                _lib.check(fn_c(P(a_in), P(wp), None, P(c), *geom, ops.ACT_NONE, c_void_p(s)))
+            else:
+                _lib.check(fn_c(P(a_in), P(wp), P(c), *geom, c_void_p(s)))
+            if ys is None:
+                _lib.check(lib.vp_bn_act_fwd_f32(P(c), P(zeros), P(ones), P(ones), P(zeros), P(y), n_out // Cout, Cout, ops.ACT_RELU, 0.0, c_void_p(s)))
+            else:
+                _lib.check(lib.vp_bn_act_fwd_split_f32(P(c), P(zeros), P(ones), P(ones), P(zeros), None, P(ys), n_out // Cout, Cout,
+                                                       ops.ACT_RELU, 0.0, c_void_p(s)))
+
+        r = ab({"fused": fused, "conv_plus_pass": separate}, args.iters, args.reps, args.warmup)
+        res[tag] = {"fused_us": r["fused"]["ms"] * 1e3, "fused_us_min_max": [r["fused"]["min"] * 1e3, r["fused"]["max"] * 1e3],
+                    "conv_plus_pass_us": r["conv_plus_pass"]["ms"] * 1e3,
+                    "conv_plus_pass_us_min_max": [r["conv_plus_pass"]["min"] * 1e3, r["conv_plus_pass"]["max"] * 1e3],
+                    "writes": "fp32" if ys is None else "split planes"}
+        print(f"  layer {tag} {prec}: fused {res[tag]['fused_us']:.1f} us  conv + pass {res[tag]['conv_plus_pass_us']:.1f} us", flush=True)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--iters", type=int, default=40, help="calls per timed window")
+    ap.add_argument("--reps", type=int, default=5, help="windows per variant (alternating)")
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--layers", action="store_true", help="per-layer fused launch vs convolution + normalise pass")
+    ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated subset of: " + ", ".join(SHAPES))
+    ap.add_argument("--precisions", default="bf16x3,f32")
+    ap.add_argument("--out", default="bench_out/infer.json")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_infer.py measures on the GPU; none is visible")
+    doc = {"tool": "tools/bench_infer.py", "device": torch.cuda.get_device_name(0), "iters": args.iters, "reps": args.reps,
+           "timing": "device events around a window of calls (host gaps included); median [min, max] over alternating repetitions",
+           "results": {}, "layers": {}}
+    for name in args.shapes.split(","):
+        C, S, z, B = SHAPES[name]
+        for prec in args.precisions.split(","):
+            doc["results"][f"{name}/{prec}"] = bench_shape(name, C, S, z, B, prec, args)
+            if args.layers:
+                doc["layers"][f"{name}/{prec}"] = bench_layers(C, S, z, B, prec, args)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()

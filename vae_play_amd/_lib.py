@@ -148,6 +148,12 @@ SIGNATURES = {
     "vp_half_sqdiff_bwd_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
     "vp_gan_head_f32": (c_int, [P, c_int, c_float, P, P, P, P]),
     "vp_smooth_l1_cat_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_float, P, P, P, P]),
+    "vp_bn_fold_f32": (c_int, [P, P, P, P, c_float, P, P, P, c_int, P]),
+    "vp_conv5_affine_supported": (c_int, [c_int] * 8),
+    "vp_conv5_gather_affine_bf16x3": (c_int, [P] * 6 + [c_int] * 7 + [P]),
+    "vp_conv5_scatter_affine_bf16x3": (c_int, [P] * 6 + [c_int] * 7 + [P]),
+    "vp_conv5_gather_affine_f32": (c_int, [P] * 6 + [c_int] * 7 + [P]),
+    "vp_conv5_scatter_affine_f32": (c_int, [P] * 6 + [c_int] * 7 + [P]),
     "vp_adam_f32": (c_int, [P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "vp_adam_outer_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "vp_rmsprop_f32": (c_int, [P, P, P, c_size_t, c_float, c_float, c_float, c_float, P]),

@@ -66,6 +66,12 @@ static int scatter_ns32(long M, int N, int C2, int phases) {
   return (C2 % 64 == 0 && tiles < 384 && 4 * C2 >= 1024) ? 2 : 1;
 }
 
+// the tile and split-K rules above for callers outside this file (the affine-epilogue launchers keep the same launch shapes)
+void f32_fast_tile(long M, long N, int gz, int* bm, int* bn) { const Tile16 t = tile32(M, N, gz); *bm = t.bm; *bn = t.bn; }
+int f32_fast_gather_nsplit(long M, int N, int Cbig) { return gather_ns32(M, N, 25 * 2 * Cbig, 2 * Cbig, false, ACT_NONE); }
+int f32_fast_scatter_nsplit(long M, int N, int Csmall, int phases) { return scatter_ns32(M, N, 2 * Csmall, phases); }
+bool f32_fast_enabled() { return f32_fast_on(); }
+
 int f32_fast_gather(const float* big, const float* w_p0, const float* bias, float* out, const ConvGeom& g0, int act, hipStream_t s, float* stat) {
   typedef ProbF16T<true, 3> P;
   P p;

@@ -24,6 +24,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "problems.h"
+#if defined(__HIPCC__)
+#include "split.h"
+#endif
 
 namespace vp {
 
@@ -309,6 +312,26 @@ using ProbT16KX = ProbT16T<false, 1>;
 using ProbT16H = ProbT16T<true, 2>;
 using ProbT16KH = ProbT16T<false, 2>;
 
+// Affine-activation epilogue (inference: eval-mode BatchNorm + ReLU folded into the convolution).  A gather / scatter descriptor wrapped
+// in ProbAff makes igemm16_kernel end with
+//     v = act(fma(acc, scale[n], shift[n]))         act = ReLU when `relu`, else none
+//     out[idx] = v            if out != nullptr       (fp32 NHWC, the descriptor's own output index)
+//     split planes of v       if out_split != nullptr (hi at out_split, lo at out_split + split_plane; split.h's rounding)
+// instead of the descriptor's store().  A compile-time property of the descriptor type (is_affine): the instantiations on the plain
+// descriptors do not see it.  K is never split here (a non-linear epilogue cannot be applied to partial sums): nsplit == 1.
+struct AffineEpi {
+  const float* scale; const float* shift;   // [N] fp32
+  u16* out_split; size_t split_plane;
+  int relu;
+};
+template <class Base>
+struct ProbAff : Base {
+  static constexpr bool AFFINE = true;
+  AffineEpi e;
+};
+template <class P, class = void> struct is_affine { static constexpr bool value = false; };
+template <class P> struct is_affine<P, decltype((void)P::AFFINE)> { static constexpr bool value = true; };
+
 // W family on split planes: slab[split][tap][cs][cb]; both operands pixel-major (KM).
 // PAIR (narrow big side, Cb = 32 | 64): one workgroup contracts TWO taps, the columns [0, Cb) of its virtual N = 2*Cb tile belong to
 // tap 2*pair and [Cb, 2*Cb) to tap 2*pair + 1 (same `small` rows, two shifted `big` pixels per staged k row): a 32-channel layer
@@ -556,6 +579,87 @@ __device__ __forceinline__ void epilogue_stats16(float* __restrict__ stat, int g
   }
 }
 
+// Affine-activation epilogue of the 32x32 accumulator layout (ProbAff descriptors): v = act(fma(acc, scale[n], shift[n])) in place, then
+//  * fp32 output straight from the registers: a lane owns one channel, so the 32 lanes of a half-wave write 128 contiguous bytes
+//    of one NHWC row per store -- the store path of the plain kernel;
+//  * split planes through LDS (the operand tiles are dead after the main loop).  Stored from the registers, 2-byte elements would leave
+//    as 64-B segments per row and plane.  Instead every wave packs (hi | lo << 16) of its 32 x (32 TN) block into its own LDS region
+//    [32 rows][32 TN + 8 dwords] (row pitch == 8 dwords mod 16: the two half-waves, four rows apart, write disjoint banks), reads it
+//    back with one lane per (row, 8 channels) -- two 16-B LDS reads -- separates the planes with four v_perm-class operations each
+//    and writes ONE 16-B store per plane: 8 channels of an NHWC row, the 4 or 8 lanes of a row contiguous (64 / 128 B per row).
+// Call with every wave past its last LDS read of the main loop (the loop ends with a barrier).
+template <class P, int BM, int BN, int WM, int WN, int TM, int TN, int LDS_BYTES>
+__device__ __forceinline__ void epilogue_affine32(const P& p, const typename P::ZCtx& z, f32x16_t (&acc)[TM][TN], unsigned char* lds, int m0,
+                                                  int n0, int wm, int wn, int li, int lh, int lane, int wave) {
+  constexpr int WCOLS = 32 * TN, S = WCOLS + 8;      // staged row pitch in dwords
+  constexpr int LPR = WCOLS / 8, RPP = 64 / LPR;      // lanes per row / rows per pass of the read-back
+  static_assert(P::F32 || 4 * 32 * S * 4 <= LDS_BYTES, "staging region of the split store");
+  const int mw = m0 + wm * (BM / WM), nw = n0 + wn * (BN / WN);
+  float sc[TN], sh[TN];
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    const int n = nw + 32 * j + li;
+    sc[j] = n < p.N ? p.e.scale[n] : 0.f;
+    sh[j] = n < p.N ? p.e.shift[n] : 0.f;
+  }
+  unsigned* const stage = reinterpret_cast<unsigned*>(lds) + wave * (32 * S);
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float v = __builtin_fmaf(acc[i][j][r], sc[j], sh[j]);      // ONE rounding: fma
+        if (p.e.relu) v = __builtin_fmaxf(v, 0.f);
+        acc[i][j][r] = v;
+      }
+    if (p.out) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int m = mw + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lh;
+        size_t base;
+        if (!p.out_index(m, 0, z, base)) continue;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int n = nw + 32 * j + li;
+          if (n < p.N) p.out[base + n] = acc[i][j][r];
+        }
+      }
+    }
+    if constexpr (!P::F32) {
+      if (p.e.out_split) {      // (workgroup-uniform)
+        if (i > 0) __syncthreads();      // the previous block's read-back is done
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            u16_t h, l;
+            split_f32(acc[i][j][r], h, l);
+            stage[((r & 3) + 8 * (r >> 2) + 4 * lh) * S + 32 * j + li] = (unsigned)h | ((unsigned)l << 16);
+          }
+        __syncthreads();
+#pragma unroll
+        for (int ps = 0; ps < 32 / RPP; ++ps) {
+          const int row = ps * RPP + lane / LPR, g8 = (lane % LPR) * 8;
+          const u32x4_t a = *reinterpret_cast<const u32x4_t*>(stage + row * S + g8);
+          const u32x4_t b = *reinterpret_cast<const u32x4_t*>(stage + row * S + g8 + 4);
+          u32x4_t hi, lo;
+          hi[0] = (a[0] & 0xffffu) | (a[1] << 16); hi[1] = (a[2] & 0xffffu) | (a[3] << 16);
+          hi[2] = (b[0] & 0xffffu) | (b[1] << 16); hi[3] = (b[2] & 0xffffu) | (b[3] << 16);
+          lo[0] = (a[0] >> 16) | (a[1] & 0xffff0000u); lo[1] = (a[2] >> 16) | (a[3] & 0xffff0000u);
+          lo[2] = (b[0] >> 16) | (b[1] & 0xffff0000u); lo[3] = (b[2] >> 16) | (b[3] & 0xffff0000u);
+          const int m = mw + 32 * i + row, n = nw + g8;
+          size_t base;
+          if (n < p.N && p.out_index(m, 0, z, base)) {      // N % 8 == 0: the 8 channels are inside or outside together
+            *reinterpret_cast<u32x4_t*>(p.e.out_split + base + n) = hi;
+            *reinterpret_cast<u32x4_t*>(p.e.out_split + p.e.split_plane + base + n) = lo;
+          }
+        }
+      }
+    }
+  }
+}
+
 // M16: contract with v_mfma_f32_16x16x32_bf16 (one MFMA = a 32-deep k-step of a 16 x 16 block; same FLOPs per cycle as the 32x32x16
 // form, lower power per product: tools/kbench measured +5 - 8 % in-kernel clock).  Gather / scatter families on bf16 pairs only
 // (k-contiguous operands: a fragment is the same 16-B read at row lane % 16, k chunk lane / 16 -- the 144-B row pitch covers all 64
@@ -565,6 +669,7 @@ template <class P, int BM, int BN, int WM, int WN, int BKT, bool FAST, bool M16 
 __global__ void __launch_bounds__(256, (M16 && BM * BN >= 128 * 128) ? 2 : 1) igemm16_kernel(const P p) {
   static_assert(!M16 || (!P::A_KM && !P::B_KM && P::MODE == 0 && BKT % 32 == 0), "16x16x32 form: k-contiguous bf16-pair operands");
   static_assert(WM * WN == 4, "4 waves per workgroup");
+  static_assert(!(M16 && is_affine<P>::value), "the affine epilogue reads the 32x32 accumulator layout");
   static_assert(BKT == 32 || BKT == 64, "K-tile depth");
   constexpr int SH = BKT == 64 ? 6 : 5;       // FAST gather/scatter kernels decompose k0 in BKT-deep channel chunks
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -904,6 +1009,10 @@ __global__ void __launch_bounds__(256, (M16 && BM * BN >= 128 * 128) ? 2 : 1) ig
     }
   }
 
+  if constexpr (is_affine<P>::value) {      // (every wave is past its last LDS read: the loop ends with a barrier)
+    epilogue_affine32<P, BM, BN, WM, WN, TM, TN, (int)sizeof(lds)>(p, z, acc, lds, m0, n0, wm, wn, li, lh, lane, wave);
+    return;
+  }
   if constexpr (P::HAS_STAT) {
     if (p.stat)      // (workgroup-uniform) every wave is past its last LDS read: the loop ends with a barrier
       epilogue_stats32<BM, BN, WM, WN, TM, TN>(p.stat, (int)(gridDim.x * gridDim.z), (int)(tz * gridDim.x) + tx, p.M, p.N, acc, lds, m0, n0,

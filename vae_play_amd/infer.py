@@ -1,0 +1,326 @@
+"""Fused VAE inference: encode / decode / reconstruct / sample of a trained model as fixed, pre-planned lists of HIP launches
+(no autograd, no per-call allocation, hipGraph-replayable), with every eval-mode BatchNorm of a convolution block folded into
+that convolution's epilogue.
+
+In eval mode BatchNorm is the per-channel affine map y = s x + t, s = gamma / sqrt(running_var + eps), t = beta - running_mean s,
+known before the launch.  A block (5x5 convolution -> BatchNorm -> ReLU) is therefore ONE launch here: the implicit-GEMM kernel
+applies act(fma(acc, s, t)) to its accumulators and writes the next layer's operand -- split bf16 planes, or fp32 -- directly
+(csrc/igemm16.h ``epilogue_affine32``), where the module path writes the fp32 convolution output and reads it back in a separate
+normalise pass.  Launch shapes the library does not fuse (``vp_conv5_affine_supported() == 0``: the few-tile layers whose plain
+launch splits K, and the first encoder block on its im2col) keep convolution + one normalise pass.
+
+Reference paths replaced: the ``eval()`` branch of VaeGan.forward (models/networks.py:248-258: sample and decode; encode ->
+reparameterise -> decode), the ``torch.no_grad()`` reconstruction inside the training loop (train.py:95-96), and the plain-VAE
+composition of Encoder (models/networks.py:72-78), reparameterize (:228-231) and Decoder (:107-112).
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional
+
+import torch
+
+from . import _lib, ops
+from .plan import PlanBuilder, _Plan, _ptr, plan_device
+
+_ACT_NONE, _ACT_SIGMOID = ops.ACT_NONE, ops.ACT_SIGMOID
+
+
+class FusedVAEInference:
+    """encode / decode / reconstruct / sample for a ``networks.VAE`` (or an Encoder / Decoder pair: ``from_modules``).
+
+    The plan SNAPSHOTS the model when it is built: convolution weights are packed into plan-owned buffers and every BatchNorm's
+    running statistics and affine parameters are folded into plan-owned scale / shift / rstd vectors, once, not per call.  After the
+    module's parameters or buffers change (training continued, ``load_state_dict``) call ``refresh()``; until then the plan keeps
+    computing with the weights it was built with -- a stale plan does NOT pick the changes up.  (Dense-layer weights, biases and the
+    dense BatchNorms' running means are read in place, so a stale plan after a change is neither the old nor the new model:
+    always ``refresh()``.)  Nothing here writes to the module: parameters, running statistics, ``num_batches_tracked`` and the
+    ``training`` flags are never modified, and the result is eval-mode arithmetic whatever ``module.training`` says.
+
+    ``precision``: "bf16x3" (5x5 layers on split-bf16 operands, three MFMAs per product) or "f32" (exact fp32 products).
+    Inputs of any number of rows run in chunks of ``batch_size``; a short last chunk is padded with zero rows (eval-mode rows are
+    independent).  Module I/O is logical NCHW fp32."""
+
+    def __init__(self, vae, batch_size: int, img_size: int, channels: int, precision: str = "bf16x3", _plan_only: bool = False):
+        self._init(vae.encoder, vae.decoder, batch_size, img_size, channels, precision, _plan_only)
+
+    @classmethod
+    def from_modules(cls, encoder, decoder, batch_size: int, img_size: int, channels: int = 1, precision: str = "bf16x3",
+                     _plan_only: bool = False) -> "FusedVAEInference":
+        """the same over an ``Encoder`` / ``Decoder`` pair, e.g. the two halves of a ``networks.VaeGan`` (``channels = 1``)"""
+        self = cls.__new__(cls)
+        self._init(encoder, decoder, batch_size, img_size, channels, precision, _plan_only)
+        return self
+
+    def _init(self, encoder, decoder, batch_size, img_size, channels, precision, plan_only):
+        if precision not in ("bf16x3", "f32"):
+            raise ValueError("precision must be 'bf16x3' or 'f32'")
+        if batch_size <= 0 or img_size < 16 or img_size & (img_size - 1):
+            raise ValueError("batch_size must be positive and img_size a power of two >= 16")
+        self.encoder, self.decoder, self.precision = encoder, decoder, precision
+        self.B, self.S, self.C = int(batch_size), int(img_size), int(channels)
+        self.Z, self.L = encoder.l_mu.out_features, len(encoder.conv)
+        if encoder.conv[0].conv.weight.shape[1] != self.C or decoder.conv[self.L][0].weight.shape[0] != self.C:
+            raise ValueError(f"the model does not take {self.C}-channel images")
+        if self.S != 8 * 2 ** self.L or len(decoder.conv) != self.L + 1:
+            raise ValueError(f"the model's {self.L} blocks do not fit {self.S}x{self.S} images")
+        self.dev = plan_device(encoder, "FusedVAEInference", plan_only)
+        self._bufs: Dict[str, torch.Tensor] = {}
+        self._graphs: Dict[str, "torch.cuda.CUDAGraph"] = {}
+        self._build()
+        if not plan_only:
+            self.refresh()
+
+    # ---- plan construction ------------------------------------------------------------------
+    def _build(self):
+        B, S, C, Z, L = self.B, self.S, self.C, self.Z, self.L
+        enc, dec = self.encoder, self.decoder
+        prep, p_enc, p_lat, p_dec = _Plan(), _Plan(), _Plan(), _Plan()
+        P = _ptr
+        b = PlanBuilder(self, self.dev, self.precision, side_on=False, wgrad_cus=(0, 0))
+        lib = b.lib
+        x3 = b.x3
+        a16 = self.precision
+
+        def use16(cin, cout):
+            return x3 and cin % 8 == 0 and cout % 8 == 0
+
+        # ---------------- encoder ----------------
+        self.x_nchw = b.buf("x_nchw", B, C, S, S)
+        self.eps = b.buf("eps", B, Z)
+        enc_ch = [C] + [blk.conv.weight.shape[0] for blk in enc.conv]
+        sp = [S // (2 ** i) for i in range(L + 1)]
+        enc16 = [use16(enc_ch[i], enc_ch[i + 1]) for i in range(L)]
+        enc0_cols = x3 and C in (1, 3) and enc_ch[1] % 8 == 0
+        enc0_cols32 = (not x3) and C in (1, 3) and enc_ch[1] % 16 == 0
+        if C > 1 and not (enc0_cols or enc0_cols32):
+            x_nhwc = b.buf("x_nhwc", B * S * S * C)
+            p_enc.add("vp_nchw_to_nhwc_f32", P(self.x_nchw), P(x_nhwc), B, C, S, S)
+        else:
+            x_nhwc = self.x_nchw          # one channel: the same memory order (the im2col kernels read NCHW themselves)
+        cur, cur_s = x_nhwc, None          # fp32 / split input of the next block
+        self.fused_layers, self.unfused_layers = [], []
+        for i, blk in enumerate(enc.conv):
+            Cin, Cout, Hs = enc_ch[i], enc_ch[i + 1], sp[i + 1]
+            n_out = B * Hs * Hs * Cout
+            fl = 50.0 * B * Hs * Hs * Cin * Cout
+            geom = (B, Hs, Hs, Cin, Cout, 2)
+            tag = f"enc{i}"
+            folded = b.bn_fold(prep, tag, blk.bn)
+            nxt16 = i + 1 < L and enc16[i + 1]
+            a = None if nxt16 else b.buf(f"{tag}.a", n_out)
+            a_s = b.sbuf(f"{tag}.as", n_out) if nxt16 else None
+            if i == 0 and (enc0_cols or enc0_cols32):
+                # first block (1 or 3 image channels): a 1x1 layer over the materialised im2col, BatchNorm as its own pass
+                KC = lib.vp_im2col5s2_cols(Cin)
+                c = b.buf(f"{tag}.c", n_out)
+                if enc0_cols:
+                    xcol, w0 = b.sbuf("enc0.xcol", B * Hs * Hs * KC), b.sbuf("enc0.w0s", Cout * KC)
+                    prep.add("vp_pack_w_im2col5_split", P(blk.conv.weight), P(w0), Cout, Cin)
+                    p_enc.add("vp_im2col5s2_split_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1)
+                    p_enc.add("vp_conv_gather_bf16x3", P(xcol), P(w0), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE,
+                              flops=fl, tag=f"{tag}.fwd")
+                else:
+                    xcol, w0 = b.buf("enc0.xcol32", B * Hs * Hs * KC), b.buf("enc0.w0", Cout * KC)
+                    prep.add("vp_pack_w_im2col5_f32", P(blk.conv.weight), P(w0), Cout, Cin)
+                    p_enc.add("vp_im2col5s2_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1)
+                    p_enc.add("vp_conv_gather_f32", P(xcol), P(w0), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE,
+                              flops=fl, tag=f"{tag}.fwd")
+                b.bn_eval(p_enc, tag, c, B * Hs * Hs, Cout, blk.bn, folded[2], a, a_s)
+                self.unfused_layers.append(tag)
+            else:
+                if enc16[i]:
+                    w = b.sbuf(f"{tag}.p0s", Cout * 25 * Cin)
+                    b.pack(blk.conv.weight, w, None, Cout, Cin, True)
+                    arith, src = a16, cur_s
+                else:
+                    w = b.buf(f"{tag}.p0", Cout * 25 * Cin)
+                    b.pack(blk.conv.weight, w, None, Cout, Cin, False)
+                    arith, src = "f32", cur
+                fused = b.conv5_bn_eval(p_enc, tag, 0, arith, src, w, geom, blk.bn, folded, a, a_s, flops=fl)
+                (self.fused_layers if fused else self.unfused_layers).append(tag)
+            cur, cur_s = a, a_s
+        size = enc_ch[-1]
+        F0 = 64 * size
+        flat = b.buf("enc.flat", B * F0)
+        p_enc.add("vp_nhwc_to_nchw_f32", P(cur), P(flat), B, size, 8, 8)
+        fc_lin, fc_bn = enc.fc[0], enc.fc[1]
+        h, hb = b.buf("enc.h", B * 1024), b.buf("enc.hb", B * 1024)
+        b.lin_fwd(p_enc, flat, fc_lin.weight, None, h, B, 1024, F0)
+        b.bn_eval(p_enc, "enc.fc", h, B, 1024, fc_bn, b.bn_fold(prep, "enc.fc", fc_bn)[2], hb)
+        self.mu, self.logvar = b.buf("mu", B, Z), b.buf("logvar", B, Z)
+        for lin, out in ((enc.l_mu, self.mu), (enc.l_var, self.logvar)):
+            b.lin_fwd(p_enc, hb, lin.weight, lin.bias, out, B, Z, 1024)
+
+        # ---------------- latent: z = eps * exp(logvar / 2) + mu ----------------
+        self.z = b.buf("z", B, Z)
+        p_lat.add("vp_latent_fwd_f32", P(self.mu), P(self.logvar), P(self.eps), P(self.z), None, B, Z)
+
+        # ---------------- decoder ----------------
+        dfc_lin, dfc_bn = dec.fc[0], dec.fc[1]
+        dsize = dec._c0
+        F1 = 64 * dsize
+        d, db = b.buf("dec.d", B * F1), b.buf("dec.db", B * F1)
+        b.lin_fwd(p_dec, self.z, dfc_lin.weight, None, d, B, F1, Z)
+        b.bn_eval(p_dec, "dec.fc", d, B, F1, dfc_bn, b.bn_fold(prep, "dec.fc", dfc_bn)[2], db)
+        dec_ch = [dsize] + [blk.conv.weight.shape[1] for blk in list(dec.conv)[:L]]
+        dec16 = [use16(dec_ch[i], dec_ch[i + 1]) for i in range(L)]
+        cur = None if dec16[0] else b.buf("dec.in", B * F1)
+        cur_s = b.sbuf("dec.in_s", B * F1) if dec16[0] else None
+        p_dec.add("vp_nchw_to_nhwc_split_f32", P(db), P(cur), P(cur_s), B, dsize, 8, 8)
+        for i in range(L):
+            blk = dec.conv[i]
+            Cin, Cout, Hs = dec_ch[i], dec_ch[i + 1], 8 * (2 ** i)
+            n_out = B * 4 * Hs * Hs * Cout
+            fl = 50.0 * B * Hs * Hs * Cin * Cout
+            geom = (B, Hs, Hs, Cin, Cout, 2)
+            tag = f"dec{i}"
+            folded = b.bn_fold(prep, tag, blk.bn)
+            # the last block feeds the final convolution, which reads fp32
+            nxt16 = i + 1 < L and dec16[i + 1]
+            u = None if nxt16 else b.buf(f"{tag}.u", n_out)
+            u_s = b.sbuf(f"{tag}.us", n_out) if nxt16 else None
+            if dec16[i]:
+                w = b.sbuf(f"{tag}.p1s", Cout * 25 * Cin)       # scatter family: [Cbig = Cout][25][Csmall = Cin]
+                b.pack(blk.conv.weight, None, w, Cin, Cout, True)
+                arith, src = a16, cur_s
+            else:
+                w = b.buf(f"{tag}.p1", Cout * 25 * Cin)
+                b.pack(blk.conv.weight, None, w, Cin, Cout, False)
+                arith, src = "f32", cur
+            fused = b.conv5_bn_eval(p_dec, tag, 1, arith, src, w, geom, blk.bn, folded, u, u_s, flops=fl)
+            (self.fused_layers if fused else self.unfused_layers).append(tag)
+            cur, cur_s = u, u_s
+        fin = dec.conv[L][0]
+        Cf = dec_ch[-1]
+        fl_fin = 50.0 * B * S * S * Cf * C
+        fp0 = b.buf("fin.p0", C * 25 * Cf)
+        b.pack(fin.weight, fp0, None, C, Cf, False)
+        xt_nhwc = b.buf("xt_nhwc", B * S * S * C)
+        if x3 and Cf == 64 and C in (1, 3):
+            p_dec.add("vp_conv5_smallout_bf16x3", P(cur), P(fp0), P(fin.bias), P(xt_nhwc), B, S, S, Cf, C, _ACT_SIGMOID,
+                      flops=fl_fin, tag="fin.fwd")
+        else:
+            b.conv5(p_dec, 0, "f32", cur, fp0, xt_nhwc, (B, S, S, Cf, C, 1), bias=fin.bias, act=_ACT_SIGMOID, flops=fl_fin, tag="fin.fwd")
+        if C > 1:
+            self.x_tilde = b.buf("x_tilde", B, C, S, S)
+            p_dec.add("vp_nhwc_to_nchw_f32", P(xt_nhwc), P(self.x_tilde), B, C, S, S)
+        else:
+            self.x_tilde = xt_nhwc.view(B, C, S, S)
+        b.finish(prep)      # the batched weight re-pack at the head of ``prep``; the dense layers' workspace
+        self._prep = prep
+        self._plans = {"encode": (p_enc,), "decode": (p_dec,), "reconstruct": (p_enc, p_lat, p_dec)}
+
+    # ---- execution ---------------------------------------------------------------------------
+    def refresh(self) -> None:
+        """Re-read the model: pack the convolution weights and fold every BatchNorm's running statistics and affine parameters into
+        the plan's constants.  Runs when the plan is built; call it again after the module's parameters or buffers changed.
+        Graphs captured before are captured again: they replay the same buffers and would see the new constants, but replays of a
+        graph instantiated BEFORE the eager re-pack launches were observed to go wrong on MI355X / ROCm (the split-K layer's
+        memset + atomic-add pair produced garbage, deterministically, while the eager list stayed right)."""
+        self._prep.run(torch.cuda.current_stream().cuda_stream)
+        if self._graphs:
+            self._graphs = {}
+            self.capture()
+
+    def _run(self, which: str) -> None:
+        g = self._graphs.get(which)
+        if g is not None:
+            g.replay()
+            return
+        s = torch.cuda.current_stream().cuda_stream
+        for plan in self._plans[which]:
+            plan.run(s)
+
+    def capture(self, warmup: int = 2):
+        """Capture encode, decode and reconstruct into one hipGraph each (linear launch lists, no allocation) and replay them from
+        then on; the results are bit-identical to the eager launches."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                for which in self._plans:
+                    self._run(which)
+        torch.cuda.current_stream().wait_stream(side)
+        graphs = {}
+        ops.CAPTURE_OK[0] = True          # (ops._stream() refuses captures it does not know: the autograd front end's)
+        try:
+            for which, plans in self._plans.items():
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    s = torch.cuda.current_stream().cuda_stream
+                    for plan in plans:
+                        plan.run(s)
+                graphs[which] = g
+        finally:
+            ops.CAPTURE_OK[0] = False
+        self._graphs = graphs
+        return graphs
+
+    def _check(self, t: torch.Tensor, what: str, tail) -> None:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise _lib.VaePlayHipError(f"FusedVAEInference: {what} must be a tensor on the HIP device (no CPU path exists)")
+        if t.dtype != torch.float32:
+            raise _lib.VaePlayHipError(f"FusedVAEInference: {what} must be fp32, got {t.dtype}")
+        if t.dim() != len(tail) + 1 or tuple(t.shape[1:]) != tuple(tail) or t.shape[0] == 0:
+            raise _lib.VaePlayHipError(f"FusedVAEInference: {what} has shape {tuple(t.shape)}, this plan takes (n, {', '.join(map(str, tail))})")
+
+    @staticmethod
+    def _load(static: torch.Tensor, t: torch.Tensor) -> None:
+        m = t.shape[0]
+        static[:m].copy_(t, non_blocking=True)
+        if m < static.shape[0]:
+            static[m:].zero_()              # a short last chunk: zero rows (rows are independent in eval mode)
+
+    def _chunks(self, n: int):
+        for i0 in range(0, n, self.B):
+            yield i0, min(self.B, n - i0)
+
+    def encode(self, x: torch.Tensor):
+        """(mu, logvar) of images x (n, C, S, S)"""
+        self._check(x, "x", (self.C, self.S, self.S))
+        n = x.shape[0]
+        mu, logvar = x.new_empty((n, self.Z)), x.new_empty((n, self.Z))
+        for i0, m in self._chunks(n):
+            self._load(self.x_nchw, x[i0:i0 + m])
+            self._run("encode")
+            mu[i0:i0 + m].copy_(self.mu[:m])
+            logvar[i0:i0 + m].copy_(self.logvar[:m])
+        return mu, logvar
+
+    def decode(self, z: torch.Tensor) -> torch.Tensor:
+        """x_tilde (n, C, S, S) of latents z (n, Z)"""
+        self._check(z, "z", (self.Z,))
+        n = z.shape[0]
+        out = z.new_empty((n, self.C, self.S, self.S))
+        for i0, m in self._chunks(n):
+            self._load(self.z, z[i0:i0 + m])
+            self._run("decode")
+            out[i0:i0 + m].copy_(self.x_tilde[:m])
+        return out
+
+    def reconstruct(self, x: torch.Tensor, eps: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None):
+        """(x_tilde, mu, logvar): encode, z = eps * exp(logvar / 2) + mu, decode -- eval mode still SAMPLES z, as the reference's
+        eval branch does; ``eps`` (n, Z) may be injected, else it is drawn from N(0, I) with ``generator``"""
+        self._check(x, "x", (self.C, self.S, self.S))
+        n = x.shape[0]
+        if eps is None:
+            eps = torch.randn((n, self.Z), dtype=torch.float32, device=x.device, generator=generator)
+        self._check(eps, "eps", (self.Z,))
+        if eps.shape[0] != n:
+            raise _lib.VaePlayHipError(f"FusedVAEInference: eps has {eps.shape[0]} rows, x has {n}")
+        out = x.new_empty((n, self.C, self.S, self.S))
+        mu, logvar = x.new_empty((n, self.Z)), x.new_empty((n, self.Z))
+        for i0, m in self._chunks(n):
+            self._load(self.x_nchw, x[i0:i0 + m])
+            self._load(self.eps, eps[i0:i0 + m])
+            self._run("reconstruct")
+            out[i0:i0 + m].copy_(self.x_tilde[:m])
+            mu[i0:i0 + m].copy_(self.mu[:m])
+            logvar[i0:i0 + m].copy_(self.logvar[:m])
+        return out, mu, logvar
+
+    def sample(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """x_p (n, C, S, S): decode z_p ~ N(0, I) (the reference's ``x is None`` branch)"""
+        if n <= 0:
+            raise ValueError("n must be positive")
+        return self.decode(torch.randn((n, self.Z), dtype=torch.float32, device=self.dev, generator=generator))

@@ -658,6 +658,36 @@ def conv5_wgrad_f16x2(big_split, shape_big, small_split, shape_small, stride: in
     return dw
 
 
+# ---- inference: eval-mode BatchNorm folded into the convolution's epilogue ---------------------
+def bn_fold(gamma, beta, running_mean, running_var, eps: float):
+    """(scale, shift, rstd) of an eval-mode BatchNorm: s = gamma / sqrt(var + eps), t = beta - mean s, rstd = 1 / sqrt(var + eps)"""
+    C = running_mean.numel()
+    scale, shift, rstd = (torch.empty(C, dtype=torch.float32, device=running_mean.device) for _ in range(3))
+    _lib.call("vp_bn_fold_f32", _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps), _p(scale), _p(shift), _p(rstd), C, _stream())
+    return scale, shift, rstd
+
+
+def conv5_affine_supported(family: int, precision: str, B: int, Hs: int, Ws: int, Cbig: int, Csmall: int, stride: int) -> bool:
+    """does this launch shape take the affine epilogue?  family 0 = gather, 1 = scatter; precision "bf16x3" | "f32" """
+    return bool(_lib.load().vp_conv5_affine_supported(family, {"bf16x3": 0, "f32": 1}[precision], B, Hs, Ws, Cbig, Csmall, stride))
+
+
+def conv5_affine(family: int, precision: str, a, shape_a, w_packed, Cout: int, scale, shift, stride: int, act: int = ACT_RELU,
+                 want_f32: bool = True, want_split: bool = False):
+    """act(scale * conv(a) + shift) in one launch.  ``a``: the input of logical shape ``shape_a`` (B, Cin, H, W) -- split planes
+    (bf16x3) or a channels_last fp32 tensor (f32); ``w_packed``: P0 (gather) / P1 (scatter) in the same arithmetic.  Returns
+    (fp32 output or None, split planes or None); the f32 entry points refuse ``want_split``."""
+    B, Cin, H, W = shape_a
+    Hs, Ws = (H // stride, W // stride) if family == 0 else (H, W)
+    Ho, Wo = (Hs, Ws) if family == 0 else (H * stride, W * stride)
+    out = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=a.device, memory_format=torch.channels_last) if want_f32 else None
+    out_s = empty_split(B * Cout * Ho * Wo, a) if want_split else None
+    name = ("vp_conv5_gather_affine_", "vp_conv5_scatter_affine_")[family] + precision
+    pa, pw = (_pv(a), _pv(w_packed)) if precision == "bf16x3" else (_p(a), _p(w_packed))
+    _lib.call(name, pa, pw, _p(scale), _p(shift), _p(out), _pv(out_s), B, Hs, Ws, Cin, Cout, stride, act, _stream())
+    return out, out_s
+
+
 # ---- k x k convolution families (models/blocks.py vocabulary) ------------------------------------------------
 def pack_w(w_ref: torch.Tensor, want_p0: bool, want_p1: bool):
     """w_ref [Cs][Cb][k][k] -> p0 [Cs][k*k][Cb], p1 [Cb][k*k][Cs]."""

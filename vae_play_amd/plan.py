@@ -341,6 +341,46 @@ class PlanBuilder:
         else:
             plan.add(name, P(a), P(w), P(out), *geom, *tail, **kw)
 
+    # ---- inference: eval-mode BatchNorm as constants ----
+    def bn_fold(self, plan, tag, bn):
+        """(scale, shift, rstd) of an eval-mode BatchNorm -- s = gamma / sqrt(running_var + eps), t = beta - running_mean s --
+        written by one launch of ``plan`` (the plan that runs once per set of weights, not per call)"""
+        P = _ptr
+        Cn = bn.running_mean.numel()
+        scale, shift, rstd = self.buf(f"{tag}.scale", Cn), self.buf(f"{tag}.shift", Cn), self.buf(f"{tag}.rstd", Cn)
+        plan.add("vp_bn_fold_f32", P(bn.weight), P(bn.bias), P(bn.running_mean), P(bn.running_var), float(bn.eps), P(scale), P(shift),
+                 P(rstd), Cn, tag=f"{tag}.fold")
+        return scale, shift, rstd
+
+    def conv5_bn_eval(self, plan, tag, family, arith, a, w, geom, bn, folded, y, y_s=None, flops=0.0) -> bool:
+        """5x5 convolution + eval-mode BatchNorm + ReLU writing fp32 ``y`` and / or split planes ``y_s``: ONE launch with the affine
+        epilogue where the library takes the launch shape (returns True), else convolution + one normalise pass over a scratch
+        buffer.  ``arith`` = "bf16x3" | "f32"; ``geom`` as conv5's; ``folded`` = bn_fold's result."""
+        P = _ptr
+        scale, shift, rstd = folded
+        qgeom = geom if family == 0 else (geom[0], geom[1], geom[2], geom[4], geom[3], geom[5])   # query takes (Cbig, Csmall)
+        if self.lib.vp_conv5_affine_supported(family, 1 if arith == "f32" else 0, *qgeom):
+            name = ("vp_conv5_gather_affine_", "vp_conv5_scatter_affine_")[family] + arith
+            plan.add(name, P(a), P(w), P(scale), P(shift), P(y), P(y_s), *geom, _ACT_RELU, flops=flops, tag=f"{tag}.fwd")
+            return True
+        Bn, Hs, Ws, stride = geom[0], geom[1], geom[2], geom[5]
+        Cout = geom[4]
+        R = Bn * Hs * Ws * (stride * stride if family == 1 else 1)
+        c = self.buf(f"{tag}.c", R * Cout)
+        self.conv5(plan, family, arith, a, w, c, geom, flops=flops, tag=f"{tag}.fwd")
+        self.bn_eval(plan, tag, c, R, Cout, bn, rstd, y, y_s)
+        return False
+
+    def bn_eval(self, plan, tag, x, R, Cn, bn, rstd, y, y_s=None):
+        """eval-mode BatchNorm + ReLU of x[R][Cn] as its own pass: running mean, folded rstd"""
+        P = _ptr
+        if y_s is None:
+            plan.add("vp_bn_act_fwd_f32", P(x), P(bn.running_mean), P(rstd), P(bn.weight), P(bn.bias), P(y), R, Cn, _ACT_RELU, 0.0,
+                     tag=f"{tag}.bn")
+        else:
+            plan.add("vp_bn_act_fwd_split_f32", P(x), P(bn.running_mean), P(rstd), P(bn.weight), P(bn.bias), P(y), P(y_s), R, Cn,
+                     _ACT_RELU, 0.0, tag=f"{tag}.bn")
+
     def bn_bwd(self, plan, x, dy, dx, R, Cn, bn, saved, dx_s=None, gfn=grad_of):
         """BatchNorm + ReLU backward; writes dx (fp32) and / or dx_s (split planes; fp16 pairs of GS * dx in "f16x2" plans) and
         the module's parameter gradients (``gfn``: where a parameter's gradient lives)"""

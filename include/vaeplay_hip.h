@@ -461,6 +461,28 @@ int vp_conv5_gather_affine_f32(const float* big, const float* w_p0, const float*
 int vp_conv5_scatter_affine_f32(const float* small, const float* w_p1, const float* scale, const float* shift, float* out_f32, void* out_split,
                                 int B, int Hs, int Ws, int Csmall, int Cbig, int stride, int act, vp_stream stream);
 
+/* ---- SCSEBlock (models/blocks.py:52-65), fp32 NHWC, forward and backward ------------------------------------------------------
+ * y[b,p,ch] = x (c[b,ch] + s[b,p]) with the channel gate c = sigmoid(W2 relu(W1 mean_p(x) + b1) + b2) (W1 [C/r][C], W2 [C][C/r], the
+ * 1x1 nn.Conv2d weights of cSE.1 / cSE.3 as they are stored) and the spatial gate s = sigmoid(sum_ch w_s[ch] x[b,p,ch] + b_s) (sSE.0);
+ * relu != 0 applies the ReLU that follows the block in StyleUp.cat_convs (models/network_Style_GAN.py:54-59) in the same store.
+ * Forward reads x twice and writes y once; it leaves pool [B][C] (the means), hid [B][C/r] (after the ReLU), cgate [B][C] and
+ * sgate [B][HW] for the backward call.  Backward reads x and dy once, writes dx and adds the pooling term into it in a last pass;
+ * the six parameter gradients are written (not accumulated), every sum in a fixed order: no atomics, bit-reproducible.
+ * dx may be null: the two stores into dx are then skipped and only the parameter gradients are produced.
+ * HW = H * W pixels per image; C <= 1024 when C % 4 == 0 (16-byte accesses), else C <= 256 (scalar accesses).  The 16-byte path
+ * needs x, y / dy, dx, cgate, w_s and ws 16-byte aligned; with an unaligned one the scalar path serves C <= 256 and a larger C is
+ * refused with VP_ERR_ARG.
+ * hidden = C / reduction of the block (>= 1: a block whose C / reduction == 0 is refused).
+ * One workspace size serves both calls. */
+size_t vp_scse_workspace_bytes(int B, int HW, int C, int hidden);
+int vp_scse_fwd_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* w_s,
+                    const float* b_s, float* y, float* pool, float* hid, float* cgate, float* sgate, int B, int HW, int C,
+                    int hidden, int relu, void* ws, size_t ws_bytes, vp_stream stream);
+int vp_scse_bwd_f32(const float* x, const float* dy, const float* w1, const float* w2, const float* w_s, const float* pool,
+                    const float* hid, const float* cgate, const float* sgate, float* dx, float* dw1, float* db1, float* dw2,
+                    float* db2, float* dw_s, float* db_s, int B, int HW, int C, int hidden, int relu, void* ws,
+                    size_t ws_bytes, vp_stream stream);
+
 /* ---- optimiser step on a flat arena (train_BE.py:62-64,131; train.py:136-140) --------------- */
 /* torch.optim.Adam semantics (no amsgrad, no weight decay); g is multiplied by grad_scale first
  * (1/world_size after a sum all-reduce). step is the 1-based step count. */

@@ -10,7 +10,8 @@ Same constructor signatures and ``state_dict`` keys as the reference:
 Convolution, normalisation + activation, bilinear resize and coordinate channels all run as HIP kernels (k x k
 implicit GEMM on the f32 MFMA path, fused norm/activation epilogues).
   SelfAttentionBlock(in_channel): q/k/v 1x1 Conv2d (+ReLU), softmax(Q K^T), gamma                     models/blocks.py:66-96
-SCSEBlock is out of scope.
+  SCSEBlock(in_channels, reduction=16): x * cSE(x) + x * sSE(x), fused forward / backward kernels      models/blocks.py:52-65
+     keys cSE.1.{weight,bias}, cSE.3.{weight,bias}, sSE.0.{weight,bias}
 """
 from __future__ import annotations
 
@@ -159,6 +160,34 @@ class SelfAttentionBlock(nn.Module):
 
     def forward(self, x):
         return F_hip.self_attention(x, self.q(x), self.k(x), self.v(x), self.gamma)
+
+
+class _NoParams(nn.Module):
+    """Stands where the reference's nn.Sequential holds a parameterless module (pooling, ReLU, Sigmoid), so that the modules with
+    parameters keep the reference's indices in the state_dict keys; the arithmetic of those modules happens in the fused kernels."""
+
+    def forward(self, x):
+        raise RuntimeError("placeholder for state_dict key numbering; the owning block computes in one fused call")
+
+
+class SCSEBlock(nn.Module):
+    """models/blocks.py:52-65: concurrent spatial and channel squeeze-and-excitation, y = x * cSE(x) + x * sSE(x), as one fused HIP
+    forward and one fused backward (functional.scse).  Keys and seeded default init equal the reference's (parameters are created
+    in its order: cSE.1, cSE.3, sSE.0).  ``forward(x, relu=True)`` also applies the ReLU that ends StyleUp.cat_convs
+    (models/network_Style_GAN.py:54-59) in the same pass; the default is the reference's forward."""
+
+    def __init__(self, in_channels, reduction=16):
+        super().__init__()
+        hidden = in_channels // reduction
+        if hidden < 1:
+            raise ValueError(f"SCSEBlock: in_channels // reduction == 0 (in_channels={in_channels}, reduction={reduction})")
+        self.cSE = nn.Sequential(_NoParams(), ConvKParams(in_channels, hidden, 1, 1, True), _NoParams(),
+                                 ConvKParams(hidden, in_channels, 1, 1, True), _NoParams())
+        self.sSE = nn.Sequential(ConvKParams(in_channels, 1, 1, 1, True), _NoParams())
+
+    def forward(self, x, relu=False):
+        c1, c3, s0 = self.cSE[1], self.cSE[3], self.sSE[0]
+        return F_hip.scse(x, c1.weight, c1.bias, c3.weight, c3.bias, s0.weight, s0.bias, relu)
 
 
 class GlobalAvgPool(nn.Module):

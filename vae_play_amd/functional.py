@@ -641,6 +641,31 @@ class _GlobalAvgPool(Function):
         return ops.global_avgpool_bwd(dy.contiguous(), ctx.shape)
 
 
+class _SCSE(Function):
+    """SCSEBlock (models/blocks.py:52-65): y = x * cSE(x) + x * sSE(x) = x (c + s), optionally followed by a ReLU in the same
+    store; fp32 whatever ``set_conv_precision`` says (no contraction here is worth an MFMA).  Backward needs x and the gates,
+    never y: the fused ReLU's mask is x > 0, because c + s > 0."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, ws, bs, relu: bool):
+        x = _cl(x)
+        y, pool, hid, cgate, sgate = ops.scse_fwd(x, w1, b1, w2, b2, ws, bs, relu)
+        if any(ctx.needs_input_grad):
+            ctx.relu = relu
+            ctx.params = (w1, b1, w2, b2, ws, bs)      # the Parameters themselves: _grad_out looks for their arena slices
+            ctx.save_for_backward(x, w1, w2, ws, pool, hid, cgate, sgate)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, w2, ws, pool, hid, cgate, sgate = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        # one kernel sequence produces all six parameter gradients; those that are wanted go straight into the arena where there is one
+        out = [_grad_out(p) if need[i + 1] else None for i, p in enumerate(ctx.params)]
+        dx, *grads = ops.scse_bwd(x, _cl(dy), w1, w2, ws, pool, hid, cgate, sgate, ctx.relu, need_dx=need[0], out=out)
+        return (dx, *(g if need[i + 1] else None for i, g in enumerate(grads)), None)
+
+
 class _SelfAttention(Function):
     """out = gamma * (V^T att^T) + x with att = softmax(Q K^T) per image (models/blocks.py:77-96); q, k, v are the
     already-projected (B, c', H, W) maps.  Per image: three HIP GEMMs + a row softmax; N = H*W = 1 (the only use in
@@ -843,6 +868,12 @@ def binary_cross_entropy(p, t, reduction: str = "sum"):
 def global_avg_pool(x):
     """nn.AdaptiveAvgPool2d((1, 1)) followed by the flatten of models/networks_BE_font.py:66: (B, C, H, W) -> (B, C)."""
     return _GlobalAvgPool.apply(x)
+
+
+def scse(x, w1, b1, w2, b2, ws, bs, relu: bool = False):
+    """SCSEBlock.forward (models/blocks.py:64-65) on the block's six parameters (cSE.1, cSE.3, sSE.0 weight and bias);
+    ``relu=True`` also applies the ReLU that follows two of these blocks in StyleUp.cat_convs (models/network_Style_GAN.py:54-59)."""
+    return _SCSE.apply(x, w1, b1, w2, b2, ws, bs, bool(relu))
 
 
 def self_attention(x, q, k, v, gamma):

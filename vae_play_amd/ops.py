@@ -405,6 +405,59 @@ def global_avgpool_bwd(dy, shape):
     return dx
 
 
+def scse_workspace_bytes(B: int, HW: int, C: int, hidden: int) -> int:
+    """Scratch bytes of scse_fwd / scse_bwd (0: the shape is refused); a host-side query, callable without a device."""
+    return int(_lib.load().vp_scse_workspace_bytes(B, HW, C, hidden))
+
+
+def _scse_hidden(x, w1) -> int:
+    """C / reduction of the block, refused here when it is 0: before anything is allocated, in the C side's words."""
+    Cr = w1.shape[0]
+    if Cr == 0:
+        raise _lib.VaePlayHipError(f"scse: hidden = 0 channels (C / reduction == 0 at C = {x.shape[1]}): the channel gate needs "
+                                   "1 <= hidden <= C")
+    return Cr
+
+
+def scse_fwd(x, w1, b1, w2, b2, ws, bs, relu: bool = False):
+    """SCSEBlock forward on a channels_last x: (y, pool (B, C), hid (B, C/r), cgate (B, C), sgate (B, H*W)); the last four are
+    what scse_bwd needs besides x.  w1 (C/r, C, 1, 1), w2 (C, C/r, 1, 1), ws (1, C, 1, 1) are the reference's conv weights."""
+    B, C, H, W = x.shape
+    Cr = _scse_hidden(x, w1)
+    assert _is_nhwc(x) and w1.shape[1] == C and tuple(w2.shape[:2]) == (C, Cr) and ws.numel() == C and bs.numel() == 1
+    w1, b1, w2, b2, ws, bs = (t.contiguous() for t in (w1, b1, w2, b2, ws, bs))
+    y = torch.empty_like(x)
+    pool, cgate = (torch.empty((B, C), dtype=torch.float32, device=x.device) for _ in range(2))
+    hid = torch.empty((B, Cr), dtype=torch.float32, device=x.device)
+    sgate = torch.empty((B, H * W), dtype=torch.float32, device=x.device)
+    wk = _ws(scse_workspace_bytes(B, H * W, C, Cr), x)
+    _lib.call("vp_scse_fwd_f32", _p(x), _p(w1), _p(b1), _p(w2), _p(b2), _p(ws), _p(bs), _p(y), _p(pool), _p(hid), _p(cgate), _p(sgate),
+              B, H * W, C, Cr, int(relu), _p(wk), wk.numel() * 4, _stream())
+    return y, pool, hid, cgate, sgate
+
+
+def scse_bwd(x, dy, w1, w2, ws, pool, hid, cgate, sgate, relu: bool = False, need_dx: bool = True, out=None):
+    """Gradients of scse_fwd: (dx, dw1, db1, dw2, db2, dws, dbs), the parameter gradients in the shapes of the parameters.
+    ``need_dx=False`` skips both passes that store dx (dx is then None); ``out`` may name, per parameter gradient, a contiguous
+    tensor of the parameter's shape to write into (None entries get a fresh tensor)."""
+    B, C, H, W = x.shape
+    Cr = _scse_hidden(x, w1)
+    assert _is_nhwc(x) and _same_layout(x, dy)
+    w1, w2, ws = w1.contiguous(), w2.contiguous(), ws.contiguous()
+    dx = torch.empty_like(x) if need_dx else None
+    shapes = ((Cr, C, 1, 1), (Cr,), (C, Cr, 1, 1), (C,), (1, C, 1, 1), (1,))
+    grads = []
+    for shape, o in zip(shapes, out or (None,) * 6):
+        if o is None:
+            o = torch.empty(shape, dtype=torch.float32, device=x.device)
+        assert tuple(o.shape) == shape and o.is_contiguous() and o.dtype == torch.float32
+        grads.append(o)
+    wk = _ws(scse_workspace_bytes(B, H * W, C, Cr), x)
+    _lib.call("vp_scse_bwd_f32", _p(x), _p(dy), _p(w1), _p(w2), _p(ws), _p(pool), _p(hid), _p(cgate), _p(sgate),
+              _p(dx) if need_dx else None, *(_p(g) for g in grads), B, H * W, C, Cr, int(relu), _p(wk), wk.numel() * 4, _stream())
+    return (dx, *grads)
+
+
 def softmax_rows_fwd(x2d):
     R, n = x2d.shape
     y = torch.empty_like(x2d)

@@ -79,8 +79,10 @@ int vp_conv5_scatter_stats_f32(const float* small, const float* w_p1, float* big
                                float eps, float momentum, float* mean, float* rstd, float* running_mean, float* running_var, void* ws,
                                size_t ws_bytes, vp_stream stream);
 
-/* ---- k x k generalisation (ks = 1, 3 or 5, padding (ks-1)/2, stride 1 or 2) -------------------------------------
+/* ---- k x k generalisation (ks = 1, 3, 4 or 5, padding (ks-1)/2, stride 1 or 2) ----------------------------------
  * The conv/norm/act vocabulary of models/blocks.py:5-34 (nn.Conv2d(k, stride, padding=(k-1)//2)); same three families.
+ * ks = 4 (padding 1) is the Style-GAN generator's kernel: myConv2d(.., 4, 2) and nn.ConvTranspose2d(in, out, 4, 2, 1),
+ * models/network_Style_GAN.py:49,95-98,116.
  * The big side is passed explicitly (Hb, Wb) so odd sizes work: Hs = floor((Hb + 2*pad - ks)/stride) + 1.
  * Weights: reference tensor W[Csmall][Cbig][ks][ks]; packed p0 = [Csmall][ks*ks][Cbig], p1 = [Cbig][ks*ks][Csmall]. */
 int vp_pack_w_f32(const float* w_ref, float* p0, float* p1, int Csmall, int Cbig, int ks, vp_stream stream);
@@ -88,12 +90,17 @@ int vp_conv_gather_f32(const float* big, const float* w_p0, const float* bias, f
                        int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride, int act, vp_stream stream);
 int vp_conv_scatter_f32(const float* small, const float* w_p1, float* big_out,
                         int B, int Hs, int Ws, int Hb, int Wb, int Csmall, int Cbig, int ks, int stride, vp_stream stream);
+/* vp_conv_scatter_f32 + bias[Cbig] added once to every output pixel (a pixel that no tap reaches holds exactly the bias): the
+ * forward pass of nn.ConvTranspose2d(in, out, 4, 2, 1) with its default bias, models/network_Style_GAN.py:49,116, without a
+ * second pass over the full-size output.  Always the generic-geometry kernel; bias == NULL is vp_conv_scatter_f32, bit for bit. */
+int vp_conv_scatter_bias_f32(const float* small, const float* w_p1, const float* bias, float* big_out,
+                             int B, int Hs, int Ws, int Hb, int Wb, int Csmall, int Cbig, int ks, int stride, vp_stream stream);
 size_t vp_conv_wgrad_workspace_bytes(int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride);
 int vp_conv_wgrad_f32(const float* big, const float* small, float* dw_ref,
                       int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride,
                       void* ws, size_t ws_bytes, vp_stream stream);
 
-/* k x k (k = 1, 3, 5; padding (k-1)/2; explicit big size Hb x Wb as for vp_conv_gather_f32) forms of the three split-bf16
+/* k x k (k = 1, 3, 4, 5; padding (k-1)/2; explicit big size Hb x Wb as for vp_conv_gather_f32) forms of the three split-bf16
  * families, for the models/blocks.py vocabulary; weights packed by vp_pack_w_split: p0 = [Csmall][k*k][Cbig],
  * p1 = [Cbig][k*k][Csmall], both as bf16 hi/lo planes. */
 int vp_pack_w_split(const float* w_ref, void* p0_split, void* p1_split, int Csmall, int Cbig, int ks, vp_stream stream);
@@ -101,6 +108,9 @@ int vp_conv_gather_bf16x3(const void* big_split, const void* w_p0_split, const f
                           int Hb, int Wb, int Cbig, int Csmall, int ks, int stride, int act, vp_stream stream);
 int vp_conv_scatter_bf16x3(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Hb, int Wb,
                            int Csmall, int Cbig, int ks, int stride, vp_stream stream);
+/* as vp_conv_scatter_bias_f32 on split planes (models/network_Style_GAN.py:49,116); bias == NULL is vp_conv_scatter_bf16x3 */
+int vp_conv_scatter_bias_bf16x3(const void* small_split, const void* w_p1_split, const float* bias, float* big_out, int B, int Hs, int Ws,
+                                int Hb, int Wb, int Csmall, int Cbig, int ks, int stride, vp_stream stream);
 size_t vp_conv_wgrad_bf16x3_workspace_bytes(int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride);
 int vp_conv_wgrad_bf16x3(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Hb, int Wb, int Cbig,
                          int Csmall, int ks, int stride, void* ws, size_t ws_bytes, vp_stream stream);

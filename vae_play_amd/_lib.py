@@ -37,6 +37,7 @@ SIGNATURES = {
     "vp_pack_w_f32": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "vp_conv_gather_f32": (c_int, [P, P, P, P] + [c_int] * 10 + [P]),
     "vp_conv_scatter_f32": (c_int, [P, P, P] + [c_int] * 9 + [P]),
+    "vp_conv_scatter_bias_f32": (c_int, [P, P, P, P] + [c_int] * 9 + [P]),
     "vp_conv_wgrad_workspace_bytes": (c_size_t, [c_int] * 9),
     "vp_conv_wgrad_f32": (c_int, [P, P, P] + [c_int] * 9 + [P, c_size_t, P]),
     "vp_split_f32": (c_int, [P, P, c_size_t, P]),
@@ -45,6 +46,7 @@ SIGNATURES = {
     "vp_pack_w_split": (c_int, [P, P, P, c_int, c_int, c_int, P]),
     "vp_conv_gather_bf16x3": (c_int, [P, P, P, P] + [c_int] * 10 + [P]),
     "vp_conv_scatter_bf16x3": (c_int, [P, P, P] + [c_int] * 9 + [P]),
+    "vp_conv_scatter_bias_bf16x3": (c_int, [P, P, P, P] + [c_int] * 9 + [P]),
     "vp_conv_wgrad_bf16x3_workspace_bytes": (c_size_t, [c_int] * 9),
     "vp_conv_wgrad_bf16x3": (c_int, [P, P, P] + [c_int] * 9 + [P, c_size_t, P]),
     "vp_conv5_gather_bf16x3": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P]),

@@ -28,12 +28,12 @@ _CONV_LRELU, _LIN_LRELU = 0.02, 0.2   # models/blocks.py:28 and :44 use differen
 
 
 class ConvKParams(nn.Module):
-    """nn.Conv2d's weight/bias layout, key names and default init; k in {1, 3, 5}, padding (k-1)//2."""
+    """nn.Conv2d's weight/bias layout, key names and default init; k in {1, 3, 4, 5}, padding (k-1)//2."""
 
     def __init__(self, in_channel: int, out_channel: int, kernel_size: int, stride: int, bias: bool):
         super().__init__()
-        if kernel_size not in (1, 3, 5) or stride not in (1, 2):
-            raise ValueError("HIP Conv2d supports kernel_size 1|3|5 and stride 1|2")
+        if kernel_size not in (1, 3, 4, 5) or stride not in (1, 2):
+            raise ValueError("HIP Conv2d supports kernel_size 1|3|4|5 and stride 1|2")
         self.stride, self.kernel_size = stride, kernel_size
         self.weight = nn.Parameter(torch.empty(out_channel, in_channel, kernel_size, kernel_size))
         self.bias = nn.Parameter(torch.empty(out_channel)) if bias else None

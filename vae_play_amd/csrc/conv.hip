@@ -24,7 +24,7 @@ extern "C" {
 
 int vp_pack_w_f32(const float* w_ref, float* p0, float* p1, int Csmall, int Cbig, int ks, vp_stream stream) {
   VP_REQUIRE(w_ref && (p0 || p1) && Csmall > 0 && Cbig > 0, "vp_pack_w_f32: bad arguments");
-  VP_REQUIRE(ks == 1 || ks == 3 || ks == 5, "vp_pack_w_f32: kernel size must be 1, 3 or 5");
+  VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "vp_pack_w_f32: kernel size must be 1, 3, 4 or 5");
   VP_REQUIRE(Csmall <= 65535 && Cbig <= 65535, "vp_pack_w_f32: channel count too large");
   return pack_w5_f32_launch(w_ref, p0, p1, Csmall, Cbig, (hipStream_t)stream, ks * ks);
 }
@@ -36,7 +36,7 @@ int vp_pack_w5_f32(const float* w_ref, float* p0, float* p1, int Csmall, int Cbi
 static int conv_check(const char* what, int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride) {
   VP_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Cbig > 0 && Csmall > 0, "%s: bad shape", what);
   VP_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2", what);
-  VP_REQUIRE(ks == 1 || ks == 3 || ks == 5, "%s: kernel size must be 1, 3 or 5", what);
+  VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "%s: kernel size must be 1, 3, 4 or 5", what);
   const int pad = (ks - 1) / 2;
   VP_REQUIRE((Hb + 2 * pad - ks) / stride + 1 == Hs && (Wb + 2 * pad - ks) / stride + 1 == Ws,
              "%s: small size must be floor((big + 2*pad - ks)/stride) + 1 (got big %dx%d small %dx%d)", what, Hb, Wb, Hs, Ws);
@@ -68,6 +68,20 @@ int vp_conv_scatter_f32(const float* small, const float* w_p1, float* big_out, i
   ProbT p = make_probT(small, w_p1, big_out, g);
   launch_igemm(p, p.M, p.N, stride * stride, (hipStream_t)stream);
   return check_launch("vp_conv_scatter_f32");
+}
+
+// Transposed convolution with its bias in the epilogue (nn.ConvTranspose2d(in, out, 4, 2, 1), models/network_Style_GAN.py:49,116):
+// always the generic-geometry kernel; a null bias is vp_conv_scatter_f32 itself.
+int vp_conv_scatter_bias_f32(const float* small, const float* w_p1, const float* bias, float* big_out, int B, int Hs, int Ws, int Hb,
+                             int Wb, int Csmall, int Cbig, int ks, int stride, vp_stream stream) {
+  if (!bias) return vp_conv_scatter_f32(small, w_p1, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream);
+  VP_REQUIRE(small && w_p1 && big_out, "vp_conv_scatter_bias_f32: null pointer");
+  int rc = conv_check("vp_conv_scatter_bias_f32", B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride);
+  if (rc) return rc;
+  ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
+  ProbT p = make_probT(small, w_p1, big_out, g, bias);
+  launch_igemm(p, p.M, p.N, stride * stride, (hipStream_t)stream);
+  return check_launch("vp_conv_scatter_bias_f32");
 }
 
 size_t vp_conv_wgrad_workspace_bytes(int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride) {

@@ -318,9 +318,14 @@ int vp_conv_scatter_bf16x3(const void* small_split, const void* w_p1_split, floa
   return scatter16<0>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream);
 }
 
+int vp_conv_scatter_bias_bf16x3(const void* small_split, const void* w_p1_split, const float* bias, float* big_out, int B, int Hs, int Ws,
+                                int Hb, int Wb, int Csmall, int Cbig, int ks, int stride, vp_stream stream) {
+  return scatter16<0>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream, 1.f, bias);
+}
+
 int vp_pack_w_split(const float* w_ref, void* p0_split, void* p1_split, int Csmall, int Cbig, int ks, vp_stream stream) {
   VP_REQUIRE(w_ref && (p0_split || p1_split) && Csmall > 0 && Cbig > 0, "vp_pack_w_split: bad arguments");
-  VP_REQUIRE(ks == 1 || ks == 3 || ks == 5, "vp_pack_w_split: kernel size must be 1, 3 or 5");
+  VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "vp_pack_w_split: kernel size must be 1, 3, 4 or 5");
   VP_REQUIRE(Csmall <= 65535 && Cbig <= 65535, "vp_pack_w_split: channel count too large");
   return pack_w5_launch<true>(w_ref, p0_split, p1_split, Csmall, Cbig, (hipStream_t)stream, "vp_pack_w_split", 0, ks * ks);
 }

@@ -122,14 +122,16 @@ static int gather16_t(const void* big_split, const void* w_p0_split, const float
 
 template <class PT>
 static int scatter16_t(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Hb, int Wb, int Csmall,
-                       int Cbig, int ks, int stride, bool plain5, vp_stream stream, float* stat = nullptr, float alpha = 1.f) {
+                       int Cbig, int ks, int stride, bool plain5, vp_stream stream, float* stat = nullptr, float alpha = 1.f,
+                       const float* bias = nullptr) {
   PT p;
   p.alpha = alpha;
+  p.bias = bias;
   p.zero = vp_zero_page();
   p.g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
   p.small = (const u16*)small_split; p.small_plane = (size_t)B * Hs * Ws * Csmall;
   p.w = (const u16*)w_p1_split; p.w_plane = (size_t)Csmall * Cbig * p.g.nt;
-  p.out = big_out; p.M = B * Hs * Ws; p.N = Cbig;
+  p.out = big_out; p.M = B * p.g.Hq * p.g.Wq; p.N = Cbig;      // the phase grid (problems.h ConvGeom): Hs x Ws for the odd kernels
   p.nsplit = scatter_nsplit(p.M, p.N, Csmall, stride, plain5);
   p.stat = stat;
   if (stat && p.nsplit != 1) return fail(VP_ERR_ARG, "vp_conv5_scatter_stats_bf16x3: this shape splits K");
@@ -165,7 +167,10 @@ static int scatter16_t(const void* small_split, const void* w_p1_split, float* b
 //   kind 1: pairs, 64x64 tile (Cb = 32) | 2: pairs, 128x128 (Cb = 64, Cs % 128 == 0) | 3: pairs, 64x128 (Cb = 64, Cs % 64 == 0)
 //   kind 4: single taps, 64x128 tile (Cs % 128 == 64, Cb % 128 == 0)
 static inline int wgrad_wide_kind(const ConvGeom& g) {
-  const bool pair_nt = g.nt == 25 || g.nt == 9;
+  // 16 taps (the 4x4 layers of models/network_Style_GAN.py:49,95-98,116) pair without a remainder; A/B knob VP_WGRAD_PAIR16=0 sends
+  // them back to single taps
+  const char* e16 = VP_GETENV("VP_WGRAD_PAIR16");
+  const bool pair_nt = g.nt == 25 || g.nt == 9 || (g.nt == 16 && !(e16 && atoi(e16) == 0));
   if (pair_nt && g.Cb == 32 && g.Cs % 64 == 0) return 1;
   if (pair_nt && g.Cb == 64 && g.Cs % 128 == 0) return 2;
   if (pair_nt && g.Cb == 64 && g.Cs % 64 == 0) return 3;
@@ -294,7 +299,7 @@ static int gather16(const void* big_split, const void* w_p0_split, const float* 
   VP_REQUIRE(big_split && w_p0_split && small_out, "vp_conv_gather_bf16x3: null pointer");
   VP_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Cbig > 0 && Csmall > 0 && Cbig % 8 == 0, "vp_conv_gather_bf16x3: Cbig must be a multiple of 8");
   VP_REQUIRE(stride == 1 || stride == 2, "vp_conv_gather_bf16x3: stride must be 1 or 2");
-  VP_REQUIRE(ks == 1 || ks == 3 || ks == 5, "vp_conv_gather_bf16x3: kernel size must be 1, 3 or 5");
+  VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "vp_conv_gather_bf16x3: kernel size must be 1, 3, 4 or 5");
   VP_REQUIRE(act == VP_ACT_NONE || act == VP_ACT_SIGMOID, "vp_conv_gather_bf16x3: epilogue supports none|sigmoid");
   const bool plain5 = ks == 5 && Hb == Hs * stride && Wb == Ws * stride;
   if constexpr (F16 != 0) {    // fp16-pair planes, f16 = products per fragment pair: always the implicit-GEMM kernels (the halo kernels read bf16 pairs)
@@ -314,11 +319,11 @@ static int gather16(const void* big_split, const void* w_p0_split, const float* 
 
 template <int F16>
 static int scatter16(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Hb, int Wb, int Csmall,
-                     int Cbig, int ks, int stride, vp_stream stream, float alpha = 1.f) {
+                     int Cbig, int ks, int stride, vp_stream stream, float alpha = 1.f, const float* bias = nullptr) {
   VP_REQUIRE(small_split && w_p1_split && big_out, "vp_conv_scatter_bf16x3: null pointer");
   VP_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Cbig > 0 && Csmall > 0 && Csmall % 8 == 0, "vp_conv_scatter_bf16x3: Csmall must be a multiple of 8");
   VP_REQUIRE(stride == 1 || stride == 2, "vp_conv_scatter_bf16x3: stride must be 1 or 2");
-  VP_REQUIRE(ks == 1 || ks == 3 || ks == 5, "vp_conv_scatter_bf16x3: kernel size must be 1, 3 or 5");
+  VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "vp_conv_scatter_bf16x3: kernel size must be 1, 3, 4 or 5");
   const bool plain5 = ks == 5 && Hb == Hs * stride && Wb == Ws * stride;
   if constexpr (F16 != 0) {
     VP_REQUIRE(alpha > 0.f, "vp_conv_scatter_f16: out_scale must be positive");
@@ -327,6 +332,8 @@ static int scatter16(const void* small_split, const void* w_p1_split, float* big
     else return plain5 ? VP_S16(ProbT16H, true) : VP_S16(ProbT16KH, false);
 #undef VP_S16
   } else {
+  // with a bias (vp_conv_scatter_bias_bf16x3): always the generic-geometry kernel, whose epilogue adds it
+  if (bias) return scatter16_t<ProbT16K>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, false, stream, nullptr, 1.f, bias);
   if (plain5 && halo_enabled())
     if (const int kind = halo_scatter_kind(B, Hs, Ws, Csmall, Cbig, stride))
       return halo_scatter_launch(kind, small_split, w_p1_split, big_out, B, Hs, Ws, Csmall, Cbig, (hipStream_t)stream);
@@ -342,7 +349,7 @@ static int wgrad16(const void* big_split, const void* small_split, float* dw_ref
   VP_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Cbig % 8 == 0 && Csmall % 8 == 0 && Cbig > 0 && Csmall > 0,
              "vp_conv_wgrad_bf16x3: channel counts must be multiples of 8");
   VP_REQUIRE(stride == 1 || stride == 2, "vp_conv_wgrad_bf16x3: stride must be 1 or 2");
-  VP_REQUIRE(ks == 1 || ks == 3 || ks == 5, "vp_conv_wgrad_bf16x3: kernel size must be 1, 3 or 5");
+  VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "vp_conv_wgrad_bf16x3: kernel size must be 1, 3, 4 or 5");
   ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
   if (const int bn = wgrad5_kind(g)) {
     if constexpr (F16 != 0) {

@@ -206,11 +206,23 @@ struct ProbT16T {
   int pair_phases = 0;       // see z_setup
   static constexpr bool HAS_STAT = true;
   float* stat = nullptr;     // see ProbF16T
+  const float* bias = nullptr;   // !K5 only: added once per output pixel (nn.ConvTranspose2d's bias, models/network_Style_GAN.py:49,116)
   struct ZCtx { int k_begin, k_end, ph, pw, th, tw, r0h, r0w, bh, bw; };   // phase geometry as in problems.h ProbT
+  // output position m -> (image b, row q, column p) of the phase grid.  K5: the grid is the small image; !K5: Hq x Wq of the
+  // geometry (problems.h ConvGeom: larger than Hs x Ws for an even kernel), M = B*Hq*Wq, `small` still addressed with Hs*Ws
+  VP_HD void m_to_bqp(int m, int& b, int& q, int& p) const {
+    if (K5) {
+      b = (int)g.dHW.div((uint32_t)m); const int rem = m - b * (g.Hs * g.Ws);
+      q = (int)g.dW.div((uint32_t)rem); p = rem - q * g.Ws;
+    } else {
+      b = (int)g.dHWq.div((uint32_t)m); const int rem = m - b * (g.Hq * g.Wq);
+      q = (int)g.dWq.div((uint32_t)rem); p = rem - q * g.Wq;
+    }
+  }
   VP_HD bool out_index(int m, int n, const ZCtx& z, size_t& idx) const {
     if (m >= M || n >= N) { idx = 0; return false; }
-    int b = (int)g.dHW.div((uint32_t)m); int rem = m - b * (g.Hs * g.Ws);
-    int q = (int)g.dW.div((uint32_t)rem), p = rem - q * g.Ws;
+    int b, q, p;
+    m_to_bqp(m, b, q, p);
     int oh = g.stride * q + z.ph, ow = g.stride * p + z.pw;
     idx = ((size_t)(b * g.Hb + oh) * g.Wb + ow) * g.Cb + n;
     return K5 || (oh < g.Hb && ow < g.Wb);
@@ -237,8 +249,9 @@ struct ProbT16T {
   }
   VP_HD ARow a_row(int m, const ZCtx&) const {
     ARow r; r.valid = m < M; int mm = r.valid ? m : 0;
-    int b = (int)g.dHW.div((uint32_t)mm); int rem = mm - b * (g.Hs * g.Ws);
-    r.q = (int)g.dW.div((uint32_t)rem); r.p = rem - r.q * g.Ws; r.pix_base = b * g.Hs * g.Ws;
+    int b;
+    m_to_bqp(mm, b, r.q, r.p);
+    r.pix_base = b * g.Hs * g.Ws;
     return r;
   }
   template <bool FAST>
@@ -293,8 +306,8 @@ struct ProbT16T {
   VP_HD size_t b_plane() const { return w_plane; }
   VP_HD void store(int m, int n, float v, const ZCtx& z) const {
     if (m >= M || n >= N) return;
-    int b = (int)g.dHW.div((uint32_t)m); int rem = m - b * (g.Hs * g.Ws);
-    int q = (int)g.dW.div((uint32_t)rem), p = rem - q * g.Ws;
+    int b, q, p;
+    m_to_bqp(m, b, q, p);
     int oh = g.stride * q + z.ph, ow = g.stride * p + z.pw;
     if (!K5 && (oh >= g.Hb || ow >= g.Wb)) return;   // odd big sizes: the last phase row/column does not exist
     float* dst = out + ((size_t)(b * g.Hb + oh) * g.Wb + ow) * g.Cb + n;
@@ -302,6 +315,7 @@ struct ProbT16T {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (nsplit > 1) { atomicAdd(dst, v); return; }
 #endif
+    if (!K5 && bias) v += bias[n];      // (K is split for the plain 5x5 layers only: never with a bias)
     *dst = v;
   }
 };

@@ -100,8 +100,13 @@ VP_HD int div_small(int t, int tw) {
 
 struct ConvGeom {
   int B, Hs, Ws, Hb, Wb, Cs, Cb, stride;
-  int ks, pad, nt;             // kernel size (1, 3 or 5), padding (ks-1)/2, taps ks*ks
+  int ks, pad, nt;             // kernel size (1, 3, 4 or 5), padding (ks-1)/2, taps ks*ks
   FastDiv dHW, dW, dCs, dCb;   // divisors Hs*Ws, Ws, Cs, Cb
+  // phase grid of the scatter family: every output phase holds Hq x Wq = ceil(Hb/stride) x ceil(Wb/stride) pixels.  Equal to
+  // Hs x Ws for the odd kernels; an even kernel (ks = 4: Hs = floor(Hb/2) at stride 2, Hb - 1 at stride 1) has Hq > Hs when the
+  // big side is odd or the stride is 1, and enumerating Hs x Ws positions would never write the last row / column of `big`.
+  int Hq, Wq;
+  FastDiv dHWq, dWq;           // divisors Hq*Wq, Wq
 };
 
 // --------------------------------------------------------------------------------------------
@@ -186,12 +191,15 @@ struct ProbF {
 // --------------------------------------------------------------------------------------------
 // T family: out_big[b, s*q+ph, s*p+pw, n] = sum_{r',q',c} small[b, q+d0-r', p+d0-q', c] * wp1[n][(ph+s*r')*5+(pw+s*q')][c]
 //   one GEMM per output phase z = ph*s+pw; taps_h = ceil((5-ph)/s); d0 = 2/s.
-//   M = B*Hs*Ws, N = Cb, K = taps_h*taps_w*Cs.
+//   M = B*Hq*Wq (the phase grid, see ConvGeom), N = Cb, K = taps_h*taps_w*Cs.  `small` is addressed with Hs*Ws; taps that
+//   leave it are predicated to zero.  bias[n] (nullable) is added once per output pixel: nn.ConvTranspose2d's bias
+//   (models/network_Style_GAN.py:49,116).
 // --------------------------------------------------------------------------------------------
 struct ProbT {
   static constexpr bool A_KM = false, B_KM = false;
   const float* small;
   const float* w;  // packed P1: [Cb][25][Cs]
+  const float* bias;  // nullable
   float* out;      // [B,Hb,Wb,Cb]
   const void* zero;
   ConvGeom g;
@@ -220,10 +228,10 @@ struct ProbT {
     ARow r;
     r.valid = m < M;
     int mm = r.valid ? m : 0;
-    int b = (int)g.dHW.div((uint32_t)mm);
-    int rem = mm - b * (g.Hs * g.Ws);
-    r.q = (int)g.dW.div((uint32_t)rem);
-    r.p = rem - r.q * g.Ws;
+    int b = (int)g.dHWq.div((uint32_t)mm);
+    int rem = mm - b * (g.Hq * g.Wq);
+    r.q = (int)g.dWq.div((uint32_t)rem);
+    r.p = rem - r.q * g.Wq;
     r.pix_base = b * g.Hs * g.Ws;
     return r;
   }
@@ -272,11 +280,12 @@ struct ProbT {
   }
   VP_HD void store(int m, int n, float v, const ZCtx& z) const {
     if (m >= M || n >= N) return;
-    int b = (int)g.dHW.div((uint32_t)m);
-    int rem = m - b * (g.Hs * g.Ws);
-    int q = (int)g.dW.div((uint32_t)rem), p = rem - q * g.Ws;
+    int b = (int)g.dHWq.div((uint32_t)m);
+    int rem = m - b * (g.Hq * g.Wq);
+    int q = (int)g.dWq.div((uint32_t)rem), p = rem - q * g.Wq;
     int oh = g.stride * q + z.ph, ow = g.stride * p + z.pw;
     if (oh >= g.Hb || ow >= g.Wb) return;   // odd big sizes: the last phase row/column does not exist
+    if (bias) v += bias[n];
     out[((size_t)(b * g.Hb + oh) * g.Wb + ow) * g.Cb + n] = v;
   }
 };
@@ -433,6 +442,8 @@ inline ConvGeom make_geom(int B, int Hs, int Ws, int Cs, int Cb, int stride, int
   g.ks = ks; g.pad = (ks - 1) / 2; g.nt = ks * ks;
   g.dHW = make_fastdiv((uint32_t)(Hs * Ws)); g.dW = make_fastdiv((uint32_t)Ws);
   g.dCs = make_fastdiv((uint32_t)Cs); g.dCb = make_fastdiv((uint32_t)Cb);
+  g.Hq = (g.Hb + stride - 1) / stride; g.Wq = (g.Wb + stride - 1) / stride;
+  g.dHWq = make_fastdiv((uint32_t)(g.Hq * g.Wq)); g.dWq = make_fastdiv((uint32_t)g.Wq);
   return g;
 }
 
@@ -447,11 +458,11 @@ inline ProbF make_probF(const float* big, const float* wp0, const float* bias, f
   return p;
 }
 
-inline ProbT make_probT(const float* small, const float* wp1, float* out, const ConvGeom& g) {
+inline ProbT make_probT(const float* small, const float* wp1, float* out, const ConvGeom& g, const float* bias = nullptr) {
   ProbT p;
   p.zero = vp_zero_page();
-  p.small = small; p.w = wp1; p.out = out; p.g = g;
-  p.M = g.B * g.Hs * g.Ws; p.N = g.Cb;
+  p.small = small; p.w = wp1; p.bias = bias; p.out = out; p.g = g;
+  p.M = g.B * g.Hq * g.Wq; p.N = g.Cb;
   p.vec = (g.Cs % 4 == 0);
   return p;
 }

@@ -6,6 +6,7 @@ Reference ops replaced (relative to the reference checkout):
   conv5x5            nn.Conv2d(k5,p2,stride)                    models/networks.py:14,100
   conv_transpose5x5  nn.ConvTranspose2d(k5,s2,p2,op1)           models/networks.py:38
   batch_norm_act     nn.BatchNorm2d/1d + F.relu (+ blocks acts) models/networks.py:16,28-29,66-67; models/blocks.py:19-30
+  conv_transpose2d   nn.ConvTranspose2d(k4,s2,p1) + bias          models/network_Style_GAN.py:49,116
   linear             nn.Linear                                  models/networks.py:65,69-70,88
   reparameterize     VaeGan.reparameterize                      models/networks.py:228-231
   kl_divergence      VaeGan.loss (kl term)                      models/networks.py:270
@@ -307,6 +308,54 @@ class _ConvT5(Function):
         return dx, dw, None
 
 
+class _ConvT4(Function):
+    """big = bias + convT4x4(small), stride 2, padding 1 (Hb = 2 Hs); weight (Csmall, Cbig, 4, 4) = nn.ConvTranspose2d layout
+    (models/network_Style_GAN.py:49,116).  The bias is added in the scatter kernel's epilogue."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        x = _cl(x)
+        B, Cs, Hs, Ws = x.shape
+        Cb = weight.shape[1]
+        ctx.x16 = _use16(weight)
+        ctx.xshape = tuple(x.shape)
+        if ctx.x16:
+            xs = _split_of(x)
+            p1 = _packed(ops.pack_w_split, weight, True)
+            y = ops.conv_scatter_bias_bf16x3(xs, x.shape, p1, bias, Cb, 4, 2, 2 * Hs, 2 * Ws)
+            x = xs          # the split copy is what the weight gradient reads
+        else:
+            p1 = _packed(ops.pack_w, weight, True)
+            y = ops.conv_scatter_bias(x, p1, bias, 4, 2, 2 * Hs, 2 * Ws)
+        ctx.has_bias = bias is not None
+        ctx.bias_param = bias
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        dy = _cl(dy)
+        dx = dw = db = None
+        if ctx.x16:
+            dys = _split_of(dy)
+            if ctx.needs_input_grad[0]:
+                p0 = _packed(ops.pack_w_split, weight, False)
+                dx = ops.conv_gather_bf16x3(dys, dy.shape, p0, weight.shape[0], None, 4, 2, ACT_NONE)
+            if ctx.needs_input_grad[1]:
+                dw = ops.conv_wgrad_bf16x3(dys, tuple(dy.shape), x, ctx.xshape, 4, 2, out=_grad_out(weight))
+        else:
+            if ctx.needs_input_grad[0]:
+                p0 = _packed(ops.pack_w, weight, False)
+                dx = ops.conv_gather(dy, p0, None, 4, 2, ACT_NONE)
+            if ctx.needs_input_grad[1]:
+                dw = ops.conv_wgrad(dy, x, 4, 2, out=_grad_out(weight))
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            B, C, H, W = dy.shape
+            db = ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * H * W, C), out=_grad_out(ctx.bias_param))
+        return dx, dw, db
+
+
 class _BatchNormAct(Function):
     """y = act(BN(x)); x is (B,C,H,W) channels_last or (B,F).  Training mode uses batch statistics
     and updates the running buffers in place with torch's momentum semantics."""
@@ -404,7 +453,7 @@ class _UnflattenNCHW(Function):
 
 
 class _ConvK(Function):
-    """nn.Conv2d(kernel k in {1,3,5}, stride 1|2, padding (k-1)//2) -- models/blocks.py:9-17."""
+    """nn.Conv2d(kernel k in {1,3,4,5}, stride 1|2, padding (k-1)//2) -- models/blocks.py:9-17."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride: int):
@@ -813,8 +862,15 @@ def linear(x, weight, bias=None):
 
 
 def conv2d(x, weight, bias=None, stride: int = 1):
-    """k x k convolution, k in {1,3,5}, padding (k-1)//2 (models/blocks.py Conv2d)."""
+    """k x k convolution, k in {1,3,4,5}, padding (k-1)//2 (models/blocks.py Conv2d)."""
     return _ConvK.apply(x, weight, bias, stride)
+
+
+def conv_transpose2d(x, weight, bias=None, stride: int = 2):
+    """nn.ConvTranspose2d(in, out, 4, 2, 1) (models/network_Style_GAN.py:49,116): weight (in, out, 4, 4), output 2H x 2W."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4) or stride != 2:
+        raise ValueError("HIP conv_transpose2d supports kernel_size 4, stride 2, padding 1")
+    return _ConvT4.apply(x, weight, bias)
 
 
 def activation(x, act: Optional[str], slope: float = 0.0):

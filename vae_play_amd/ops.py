@@ -776,6 +776,17 @@ def conv_scatter(small, w_p1, ks: int, stride: int, Hb: int, Wb: int):
     return out
 
 
+def conv_scatter_bias(small, w_p1, bias: Optional[torch.Tensor], ks: int, stride: int, Hb: int, Wb: int):
+    """conv_scatter + bias[Cb] on every output pixel in the same launch (nn.ConvTranspose2d's forward, models/network_Style_GAN.py:49,116)."""
+    assert _is_nhwc(small)
+    B, Cs, Hs, Ws = small.shape
+    Cb = w_p1.shape[0]
+    assert bias is None or (bias.shape == (Cb,) and bias.is_contiguous())
+    out = empty_cl(B, Cb, Hb, Wb, small)
+    _lib.call("vp_conv_scatter_bias_f32", _p(small), _p(w_p1), _p(bias), _p(out), B, Hs, Ws, Hb, Wb, Cs, Cb, ks, stride, _stream())
+    return out
+
+
 def conv_wgrad(big, small, ks: int, stride: int, out: Optional[torch.Tensor] = None):
     assert _is_nhwc(big) and _is_nhwc(small)
     B, Cb, Hb, Wb = big.shape
@@ -811,6 +822,16 @@ def conv_scatter_bf16x3(small_split, shape_small, w_p1_split, Cb: int, ks: int, 
     B, Cs, Hs, Ws = shape_small
     out = torch.empty((B, Cb, Hb, Wb), dtype=torch.float32, device=small_split.device, memory_format=torch.channels_last)
     _lib.call("vp_conv_scatter_bf16x3", _pv(small_split), _pv(w_p1_split), _p(out), B, Hs, Ws, Hb, Wb, Cs, Cb, ks, stride, _stream())
+    return out
+
+
+def conv_scatter_bias_bf16x3(small_split, shape_small, w_p1_split, bias: Optional[torch.Tensor], Cb: int, ks: int, stride: int, Hb: int,
+                             Wb: int):
+    B, Cs, Hs, Ws = shape_small
+    assert bias is None or (bias.shape == (Cb,) and bias.is_contiguous())
+    out = torch.empty((B, Cb, Hb, Wb), dtype=torch.float32, device=small_split.device, memory_format=torch.channels_last)
+    _lib.call("vp_conv_scatter_bias_bf16x3", _pv(small_split), _pv(w_p1_split), _p(bias), _p(out), B, Hs, Ws, Hb, Wb, Cs, Cb, ks, stride,
+              _stream())
     return out
 
 

@@ -293,6 +293,19 @@ int vp_instnorm_act_fwd_split_f32(const float* x, float* y, void* y_split, float
                                   int act, float slope, void* ws, size_t ws_bytes, vp_stream stream);
 int vp_instnorm_act_bwd_split_f32(const float* x, const float* dy, const float* mean, const float* rstd, float* dx, void* dx_split, int B,
                                   int R, int C, int act, float slope, void* ws, size_t ws_bytes, vp_stream stream);
+/* label-gated pair of convolutions, conv_1(x) * (1 - label) + conv_2(x) * label (models/network_Style_GAN.py:72-79), behind ONE
+ * convolution whose weights are the two branches' stacked along the output channel: u is [B][R = H*W][2C] NHWC with branch 1 in
+ * channels [0, C) and branch 2 in [C, 2C); label [B] floats; y [B][R][C] = (1 - label[b]) * act(pre_1) + label[b] * act(pre_2).
+ * norm = 1: pre_j is InstanceNorm2d(affine=False, eps) of branch j (statistics over the 2C channels; mean / rstd [B][2C] are outputs
+ * of the forward and inputs of the backward; needs the workspace).  norm = 0: pre_j = u_j; mean, rstd, ws may be null.
+ * y_split / du_split (nullable, C % 4 == 0): bf16 hi/lo planes of y (plane = B*R*C elements) / du (plane = B*R*2C), laid out as by
+ * vp_instnorm_act_fwd_split_f32.  The label gets no gradient.  Fixed-order reductions: two runs are bit-identical. */
+size_t vp_pair_blend_workspace_bytes(int B, int R, int C);
+int vp_pair_blend_fwd_f32(const float* u, const float* label, float* y, void* y_split, float* mean, float* rstd, int B, int R, int C,
+                          int norm, float eps, int act, float slope, void* ws, size_t ws_bytes, vp_stream stream);
+int vp_pair_blend_bwd_f32(const float* u, const float* dy, const float* label, const float* mean, const float* rstd, float* du,
+                          void* du_split, int B, int R, int C, int norm, int act, float slope, void* ws, size_t ws_bytes,
+                          vp_stream stream);
 /* plain activation (conv + bias + act blocks of models/blocks.py:24-30 with bn=None) */
 int vp_act_fwd_f32(const float* x, float* y, size_t n, int act, float slope, vp_stream stream);
 /* dx = dy * act'(.) evaluated from the OUTPUT y (relu/lrelu/tanh/sigmoid); dx may alias dy */

@@ -582,6 +582,237 @@ inline size_t bn_ws_floats(int R, int C) {
   return (size_t)2 * g.chunks_r * C + (size_t)2 * C;   // partial slabs + (sum_g, sum_gx)
 }
 
+// ---- label-gated pair of convolutions (models/network_Style_GAN.py:72-79) -----------------------------------------------------------
+// u [B][R][2C] is the output of ONE convolution whose weights are conv_1's and conv_2's stacked along the output channel: channels
+// [0, C) are branch 1, [C, 2C) branch 2.  y[b][r][c] = w1 * act(pre(u[b][r][c])) + w2 * act(pre(u[b][r][C + c])) with w2 = label[b],
+// w1 = 1 - label[b] and pre = InstanceNorm (norm = 1: the statistics are the InstanceNorm kernels above run over 2C channels) or the
+// identity (norm = 0).  Same (16 float4 columns x 16 rows) thread map as the tiled kernels above, over the C output channels; VEC =
+// (C % 4 == 0) takes 16-B loads and stores, the other instantiation guards every element.
+template <bool VEC>
+__device__ __forceinline__ vp_f32x4 pair_ld4(const float* __restrict__ p, int nv) {
+  if (VEC) return *reinterpret_cast<const vp_f32x4*>(p);
+  vp_f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
+  return v;
+}
+template <bool VEC>
+__device__ __forceinline__ void pair_st4(float* __restrict__ p, const vp_f32x4& v, int nv) {
+  if (VEC) { *reinterpret_cast<vp_f32x4*>(p) = v; return; }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) if (j < nv) p[j] = v[j];
+}
+// per-thread constants of one branch: mean / rstd of its 4 channels (identity when norm = 0)
+struct PairStat { float mu[4], rs[4]; };
+__device__ __forceinline__ PairStat pair_stat(const float* __restrict__ mean, const float* __restrict__ rstd, int c, int nv, int norm) {
+  PairStat s;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool ok = norm && j < nv;
+    s.mu[j] = ok ? mean[c + j] : 0.f;
+    s.rs[j] = ok ? rstd[c + j] : 1.f;
+  }
+  return s;
+}
+// pre-activation value, as the forward computes it (the backward rebuilds the activation mask from the same expression)
+__device__ __forceinline__ float pair_pre(float v, float mu, float rs, int norm) { return norm ? bn_pre(v, mu, rs, 1.f, 0.f) : v; }
+// g = w * dy * act'(pre): one expression for the partial sums and the apply pass
+__device__ __forceinline__ float pair_g(float w, float d, float pre, int act, float slope) { return (w * d) * act_grad_pre(pre, act, slope); }
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) pair_blend_fwd_kernel(const float* __restrict__ u, const float* __restrict__ label,
+                                                             const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                             float* __restrict__ y, u16_t* __restrict__ y_split, int R, int C,
+                                                             int rows_per_chunk, int norm, int act, float slope) {
+  const int b = blockIdx.z, C2 = 2 * C;
+  const size_t bys = (size_t)R * C;
+  u += (size_t)b * 2 * bys; y += (size_t)b * bys;
+  const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
+  const int c = blockIdx.y * BN_CH + tx * 4;
+  if (c >= C) return;
+  const int nv = min(4, C - c);
+  const float w2 = label[b], w1 = 1.f - w2;
+  const PairStat s1 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, c, nv, norm);
+  const PairStat s2 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, C + c, nv, norm);
+  const size_t n = bys * gridDim.z;                   // one split plane spans all images
+  if (y_split) y_split += (size_t)b * bys;
+  const int r0 = blockIdx.x * rows_per_chunk;
+  const int r1 = min(R, r0 + rows_per_chunk);
+  auto emit = [&](int r, const vp_f32x4& va, const vp_f32x4& vb) {
+    vp_f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float a1 = act_apply(pair_pre(va[j], s1.mu[j], s1.rs[j], norm), act, slope);
+      const float a2 = act_apply(pair_pre(vb[j], s2.mu[j], s2.rs[j], norm), act, slope);
+      o[j] = fmaf(w2, a2, w1 * a1);
+    }
+    const size_t off = (size_t)r * C + c;
+    pair_st4<VEC>(y + off, o, nv);
+    if (VEC && y_split) store_split4(y_split, n, off, o[0], o[1], o[2], o[3]);
+  };
+  int r = r0 + ty;
+  for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {        // eight independent loads in flight
+    vp_f32x4 va[4], vb[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float* p = u + (size_t)(r + k * BN_TY) * C2 + c;
+      va[k] = pair_ld4<VEC>(p, nv);
+      vb[k] = pair_ld4<VEC>(p + C, nv);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) emit(r + k * BN_TY, va[k], vb[k]);
+  }
+  for (; r < r1; r += BN_TY) {
+    const float* p = u + (size_t)r * C2 + c;
+    emit(r, pair_ld4<VEC>(p, nv), pair_ld4<VEC>(p + C, nv));
+  }
+}
+
+// (sum g1, sum g1 * xhat1, sum g2, sum g2 * xhat2) per (image, channel, row chunk) in one read of u and dy, written into the slab
+// layout of bn_partial_kernel<1> over 2C channels, so that bn_bwd_final_kernel finishes it
+template <bool VEC>
+__global__ void __launch_bounds__(256) pair_blend_partial_kernel(const float* __restrict__ u, const float* __restrict__ dy,
+                                                                 const float* __restrict__ label, const float* __restrict__ mean,
+                                                                 const float* __restrict__ rstd, float* __restrict__ part, int R, int C,
+                                                                 int rows_per_chunk, int act, float slope, size_t bps) {
+  __shared__ float sh[4][BN_TY][BN_CH + 4];
+  const int b = blockIdx.z, C2 = 2 * C;
+  const size_t bys = (size_t)R * C;
+  u += (size_t)b * 2 * bys; dy += (size_t)b * bys; part += (size_t)b * bps;
+  const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
+  const int c = blockIdx.y * BN_CH + tx * 4;
+  const int nv = min(4, C - c);                        // <= 0: this column of threads has no channel
+  float s[4][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[q][j] = 0.f;
+  if (c < C) {
+    const float w2 = label[b], w1 = 1.f - w2;
+    const PairStat s1 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, c, nv, 1);
+    const PairStat s2 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, C + c, nv, 1);
+    auto accum = [&](const vp_f32x4& va, const vp_f32x4& vb, const vp_f32x4& d) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float x1 = (va[j] - s1.mu[j]) * s1.rs[j], x2 = (vb[j] - s2.mu[j]) * s2.rs[j];
+        const float g1 = pair_g(w1, d[j], pair_pre(va[j], s1.mu[j], s1.rs[j], 1), act, slope);
+        const float g2 = pair_g(w2, d[j], pair_pre(vb[j], s2.mu[j], s2.rs[j], 1), act, slope);
+        s[0][j] += g1;
+        s[1][j] = fmaf(g1, x1, s[1][j]);
+        s[2][j] += g2;
+        s[3][j] = fmaf(g2, x2, s[3][j]);
+      }
+    };
+    const int r0 = blockIdx.x * rows_per_chunk;
+    const int r1 = min(R, r0 + rows_per_chunk);
+    int r = r0 + ty;
+    // four rows per trip, summed in row order: the result does not depend on the unrolling
+    for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {
+      vp_f32x4 va[4], vb[4], vd[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float* p = u + (size_t)(r + k * BN_TY) * C2 + c;
+        va[k] = pair_ld4<VEC>(p, nv);
+        vb[k] = pair_ld4<VEC>(p + C, nv);
+        vd[k] = pair_ld4<VEC>(dy + (size_t)(r + k * BN_TY) * C + c, nv);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) accum(va[k], vb[k], vd[k]);
+    }
+    for (; r < r1; r += BN_TY) {
+      const float* p = u + (size_t)r * C2 + c;
+      accum(pair_ld4<VEC>(p, nv), pair_ld4<VEC>(p + C, nv), pair_ld4<VEC>(dy + (size_t)r * C + c, nv));
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[q][ty][tx * 4 + j] = s[q][j];
+  __syncthreads();
+  const int q = threadIdx.x / BN_CH, cc = threadIdx.x % BN_CH;        // 4 sums x 64 channels = 256 threads
+  float t = 0.f;
+#pragma unroll
+  for (int k = 0; k < BN_TY; ++k) t += sh[q][k][cc];
+  const int cg = blockIdx.y * BN_CH + cc;
+  // q & 1: 0 = sum g, 1 = sum g * xhat (the two slabs of bn_partial_kernel); q >> 1: branch, at channel offset C
+  if (cg < C) part[((size_t)(q & 1) * gridDim.x + blockIdx.x) * C2 + (q >> 1) * C + cg] = t;
+}
+
+// du_j = rstd_j * (g_j - (sum g_j + xhat_j * sum g_j xhat_j) / R)  (norm = 1)  |  g_j  (norm = 0), both halves in one pass
+template <bool VEC>
+__global__ void __launch_bounds__(256) pair_blend_bwd_kernel(const float* __restrict__ u, const float* __restrict__ dy,
+                                                             const float* __restrict__ label, const float* __restrict__ mean,
+                                                             const float* __restrict__ rstd, const float* __restrict__ sum_g,
+                                                             const float* __restrict__ sum_gx, float* __restrict__ du,
+                                                             u16_t* __restrict__ du_split, int R, int C, int rows_per_chunk, float invR,
+                                                             int norm, int act, float slope) {
+  const int b = blockIdx.z, C2 = 2 * C;
+  const size_t bys = (size_t)R * C;
+  u += (size_t)b * 2 * bys; du += (size_t)b * 2 * bys; dy += (size_t)b * bys;
+  const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
+  const int c = blockIdx.y * BN_CH + tx * 4;
+  if (c >= C) return;
+  const int nv = min(4, C - c);
+  const float w2 = label[b], w1 = 1.f - w2;
+  const PairStat s1 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, c, nv, norm);
+  const PairStat s2 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, C + c, nv, norm);
+  float k0[2][4], k1[2][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool ok = norm && j < nv;
+    const size_t i1 = (size_t)b * C2 + c + j, i2 = i1 + C;
+    k0[0][j] = ok ? sum_g[i1] * invR : 0.f; k1[0][j] = ok ? sum_gx[i1] * invR : 0.f;
+    k0[1][j] = ok ? sum_g[i2] * invR : 0.f; k1[1][j] = ok ? sum_gx[i2] * invR : 0.f;
+  }
+  const size_t n = 2 * bys * gridDim.z;
+  if (du_split) du_split += (size_t)b * 2 * bys;
+  // bn=None without an activation (conv1, conv2 of the generator): du_j = w_j * dy, u is not read
+  const bool need_u = norm || act != ACT_NONE;
+  const vp_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  const int r0 = blockIdx.x * rows_per_chunk;
+  const int r1 = min(R, r0 + rows_per_chunk);
+  auto emit = [&](int r, const vp_f32x4& va, const vp_f32x4& vb, const vp_f32x4& d) {
+    vp_f32x4 oa, ob;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float g1 = pair_g(w1, d[j], pair_pre(va[j], s1.mu[j], s1.rs[j], norm), act, slope);
+      const float g2 = pair_g(w2, d[j], pair_pre(vb[j], s2.mu[j], s2.rs[j], norm), act, slope);
+      if (norm) {
+        const float x1 = (va[j] - s1.mu[j]) * s1.rs[j], x2 = (vb[j] - s2.mu[j]) * s2.rs[j];
+        oa[j] = s1.rs[j] * (g1 - fmaf(x1, k1[0][j], k0[0][j]));
+        ob[j] = s2.rs[j] * (g2 - fmaf(x2, k1[1][j], k0[1][j]));
+      } else {
+        oa[j] = g1;
+        ob[j] = g2;
+      }
+    }
+    const size_t off = (size_t)r * C2 + c;
+    pair_st4<VEC>(du + off, oa, nv);
+    pair_st4<VEC>(du + off + C, ob, nv);
+    if (VEC && du_split) {
+      store_split4(du_split, n, off, oa[0], oa[1], oa[2], oa[3]);
+      store_split4(du_split, n, off + C, ob[0], ob[1], ob[2], ob[3]);
+    }
+  };
+  int r = r0 + ty;
+  for (; r + BN_TY < r1; r += 2 * BN_TY) {              // six independent loads in flight
+    vp_f32x4 va[2], vb[2], vd[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const float* p = u + (size_t)(r + k * BN_TY) * C2 + c;
+      va[k] = need_u ? pair_ld4<VEC>(p, nv) : zero;
+      vb[k] = need_u ? pair_ld4<VEC>(p + C, nv) : zero;
+      vd[k] = pair_ld4<VEC>(dy + (size_t)(r + k * BN_TY) * C + c, nv);
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) emit(r + k * BN_TY, va[k], vb[k], vd[k]);
+  }
+  for (; r < r1; r += BN_TY) {
+    const float* p = u + (size_t)r * C2 + c;
+    emit(r, need_u ? pair_ld4<VEC>(p, nv) : zero, need_u ? pair_ld4<VEC>(p + C, nv) : zero, pair_ld4<VEC>(dy + (size_t)r * C + c, nv));
+  }
+}
+
 }  // namespace vp
 
 using namespace vp;
@@ -788,6 +1019,87 @@ int vp_instnorm_act_bwd_split_f32(const float* x, const float* dy, const float* 
                                   int R, int C, int act, float slope, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(dx_split, "vp_instnorm_act_bwd_split_f32: null split output");
   return instnorm_act_bwd_impl(x, dy, mean, rstd, dx, dx_split, B, R, C, act, slope, ws, ws_bytes, stream);
+}
+
+// ---- label-gated pair: InstanceNorm statistics over the 2C stacked channels, then one blend pass ---------------------------------
+size_t vp_pair_blend_workspace_bytes(int B, int R, int C) { return (size_t)B * bn_ws_floats(R, 2 * C) * sizeof(float); }
+
+int vp_pair_blend_fwd_f32(const float* u, const float* label, float* y, void* y_split, float* mean, float* rstd, int B, int R, int C,
+                          int norm, float eps, int act, float slope, void* ws, size_t ws_bytes, vp_stream stream) {
+  VP_REQUIRE(u && label && y && B > 0 && B <= 65535 && R > 0 && C > 0 && C <= (1 << 29), "vp_pair_blend_fwd_f32: bad arguments");
+  VP_REQUIRE(!norm || (mean && rstd && ws), "vp_pair_blend_fwd_f32: norm = 1 needs mean, rstd and a workspace");
+  VP_REQUIRE(!y_split || C % 4 == 0, "vp_pair_blend_fwd_f32: split planes need C to be a multiple of 4");
+  hipStream_t s = (hipStream_t)stream;
+  if (norm) {
+    if (ws_bytes < vp_pair_blend_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_pair_blend_fwd_f32: workspace too small");
+    const int C2 = 2 * C;
+    const BnGrid g = bn_grid(R, C2);
+    const size_t bxs = (size_t)R * C2, bps = (size_t)2 * g.chunks_r * C2;
+    float* part = (float*)ws;
+    hipLaunchKernelGGL((bn_partial_kernel<0>), dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, u, (const float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, R, C2,
+                       g.rows_per_chunk, 0, 0.f, bxs, bps);
+    int rc = check_launch("vp_pair_blend_fwd_f32(partial)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C2 + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, g.chunks_r, R, C2,
+                       eps, 0.f, mean, rstd, (float*)nullptr, (float*)nullptr, u, bps, bxs);
+    rc = check_launch("vp_pair_blend_fwd_f32(final)");
+    if (rc) return rc;
+  }
+  const BnGrid ga = bn_apply_grid(R, C);
+  const dim3 grid(ga.chunks_r, ga.chunks_c, B);
+  if (C % 4 == 0)
+    hipLaunchKernelGGL((pair_blend_fwd_kernel<true>), grid, dim3(256), 0, s, u, label, (const float*)mean, (const float*)rstd, y,
+                       (u16_t*)y_split, R, C, ga.rows_per_chunk, norm ? 1 : 0, act, slope);
+  else
+    hipLaunchKernelGGL((pair_blend_fwd_kernel<false>), grid, dim3(256), 0, s, u, label, (const float*)mean, (const float*)rstd, y,
+                       (u16_t*)nullptr, R, C, ga.rows_per_chunk, norm ? 1 : 0, act, slope);
+  return check_launch("vp_pair_blend_fwd_f32(apply)");
+}
+
+int vp_pair_blend_bwd_f32(const float* u, const float* dy, const float* label, const float* mean, const float* rstd, float* du,
+                          void* du_split, int B, int R, int C, int norm, int act, float slope, void* ws, size_t ws_bytes,
+                          vp_stream stream) {
+  VP_REQUIRE(u && dy && label && du && B > 0 && B <= 65535 && R > 0 && C > 0 && C <= (1 << 29), "vp_pair_blend_bwd_f32: bad arguments");
+  VP_REQUIRE(!norm || (mean && rstd && ws), "vp_pair_blend_bwd_f32: norm = 1 needs mean, rstd and a workspace");
+  VP_REQUIRE(!du_split || C % 4 == 0, "vp_pair_blend_bwd_f32: split planes need C to be a multiple of 4");
+  hipStream_t s = (hipStream_t)stream;
+  const bool vec = C % 4 == 0;
+  const float* sum_g = nullptr;
+  const float* sum_gx = nullptr;
+  if (norm) {
+    if (ws_bytes < vp_pair_blend_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_pair_blend_bwd_f32: workspace too small");
+    const int C2 = 2 * C;
+    const BnGrid g = bn_grid(R, C2);                  // row chunks and slab layout of the 2C-channel InstanceNorm backward
+    const size_t bps = (size_t)2 * g.chunks_r * C2;
+    float* part = (float*)ws;
+    float* sg = part + (size_t)B * bps;               // [B][2C], then sum_gx [B][2C]
+    float* sgx = sg + (size_t)B * C2;
+    const dim3 grid(g.chunks_r, (C + BN_CH - 1) / BN_CH, B);
+    if (vec)
+      hipLaunchKernelGGL((pair_blend_partial_kernel<true>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, part, R, C, g.rows_per_chunk,
+                         act, slope, bps);
+    else
+      hipLaunchKernelGGL((pair_blend_partial_kernel<false>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, part, R, C, g.rows_per_chunk,
+                         act, slope, bps);
+    int rc = check_launch("vp_pair_blend_bwd_f32(partial)");
+    if (rc) return rc;
+    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C2 + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, g.chunks_r, C2, sg,
+                       sgx, (float*)nullptr, (float*)nullptr, bps);
+    rc = check_launch("vp_pair_blend_bwd_f32(final)");
+    if (rc) return rc;
+    sum_g = sg; sum_gx = sgx;
+  }
+  const BnGrid ga = bn_apply_grid(R, C);
+  const dim3 grid(ga.chunks_r, ga.chunks_c, B);
+  const float invR = 1.f / (float)R;
+  if (vec)
+    hipLaunchKernelGGL((pair_blend_bwd_kernel<true>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, sum_g, sum_gx, du, (u16_t*)du_split, R,
+                       C, ga.rows_per_chunk, invR, norm ? 1 : 0, act, slope);
+  else
+    hipLaunchKernelGGL((pair_blend_bwd_kernel<false>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, sum_g, sum_gx, du, (u16_t*)nullptr, R,
+                       C, ga.rows_per_chunk, invR, norm ? 1 : 0, act, slope);
+  return check_launch("vp_pair_blend_bwd_f32(apply)");
 }
 
 int vp_bn_small_fwd_f32(const float* x, int R, int C, float eps, float momentum, const float* gamma, const float* beta, float* mean,

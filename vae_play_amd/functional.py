@@ -7,6 +7,7 @@ Reference ops replaced (relative to the reference checkout):
   conv_transpose5x5  nn.ConvTranspose2d(k5,s2,p2,op1)           models/networks.py:38
   batch_norm_act     nn.BatchNorm2d/1d + F.relu (+ blocks acts) models/networks.py:16,28-29,66-67; models/blocks.py:19-30
   conv_transpose2d   nn.ConvTranspose2d(k4,s2,p1) + bias          models/network_Style_GAN.py:49,116
+  pair_blend         myConv2d: norm + act + label blend of a stacked conv   models/network_Style_GAN.py:72-79
   linear             nn.Linear                                  models/networks.py:65,69-70,88
   reparameterize     VaeGan.reparameterize                      models/networks.py:228-231
   kl_divergence      VaeGan.loss (kl term)                      models/networks.py:270
@@ -68,7 +69,7 @@ def _grad_out(param) -> Optional[torch.Tensor]:
     without a kernel, where it would otherwise add a fresh tensor onto the zeroed arena -- one small add per parameter tensor
     and step (114 launches, 6 % of the VAE-GAN step).  A parameter used twice in one graph gets the view once (its hook clears
     the marker after accumulation); further contributions take the ordinary path and are added by autograd."""
-    if param is None or param.grad is not None or not _DIRECT_GRADS:
+    if param is None or not param.is_leaf or param.grad is not None or not _DIRECT_GRADS:      # (not a leaf: myConv2d's stacked weight)
         return None
     arena = getattr(param, "_vp_arena", None)
     if arena is None or getattr(param, "_vp_pending", False) or torch.is_grad_enabled():
@@ -603,6 +604,31 @@ class _InstanceNormAct(Function):
         return ops.instnorm_act_bwd(x, _cl(dy), mean, rstd, ctx.act, ctx.slope), None, None, None
 
 
+class _PairBlend(Function):
+    """conv_1(x) * (1 - label) + conv_2(x) * label behind one stacked convolution (models/network_Style_GAN.py:72-79): u holds
+    both branches along the channel, norm = InstanceNorm2d of each branch before the activation.  ``label`` (B,) is a constant."""
+
+    @staticmethod
+    def forward(ctx, u, label, norm: bool, eps: float, act: int, slope: float):
+        u = _cl(u)
+        C = u.shape[1] // 2
+        ctx.split = _PRECISION == "bf16x3" and _BWD_SPLIT and C % 8 == 0       # as _InstanceNormAct
+        y, mean, rstd, ys = ops.pair_blend_fwd(u, label, norm, eps, act, slope, want_split=ctx.split)
+        if ys is not None:
+            y._vp_split = (ys, y._version)
+        ctx.norm, ctx.act, ctx.slope = norm, act, slope
+        ctx.save_for_backward(u, label, mean, rstd)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, label, mean, rstd = ctx.saved_tensors
+        du, dus = ops.pair_blend_bwd(u, _cl(dy), label, mean, rstd, ctx.norm, ctx.act, ctx.slope, want_split=ctx.split)
+        if dus is not None:
+            du._vp_split = (dus, du._version)
+        return du, None, None, None, None, None
+
+
 class _Upsample2x(Function):
     """F.interpolate(scale_factor=2, mode='bilinear') -- models/blocks.py:145."""
 
@@ -880,6 +906,16 @@ def activation(x, act: Optional[str], slope: float = 0.0):
 
 def instance_norm_act(x, eps: float = 1e-5, act: Optional[str] = None, slope: float = 0.0):
     return _InstanceNormAct.apply(x, eps, ACT_CODES[act], slope)
+
+
+def pair_blend(u, label, norm: bool = False, eps: float = 1e-5, act: Optional[str] = None, slope: float = 0.0):
+    """Label-gated blend of the two halves of ``u`` (B, 2C, H, W) -> (B, C, H, W): (1 - label[b]) * act(n(u[:, :C])) +
+    label[b] * act(n(u[:, C:])), n = InstanceNorm2d(eps) with ``norm`` else the identity.  ``label``: B elements of any dtype,
+    a constant (no gradient)."""
+    if u.dim() != 4 or u.shape[1] % 2 != 0 or label.numel() != u.shape[0]:
+        raise ValueError("pair_blend: u must be (B, 2C, H, W) and label must have B elements")
+    label = label.detach().reshape(-1).to(device=u.device, dtype=torch.float32).contiguous()
+    return _PairBlend.apply(u, label, bool(norm), eps, ACT_CODES[act], slope)
 
 
 def upsample2x_bilinear(x):

@@ -1,13 +1,18 @@
-"""Drop-in classes for kungyao/vae-play's ``models/network_Style_GAN.py`` on the HIP back end: the 4x4 stride-2 transposed
-convolution of the Style-GAN generator and its first user, the decoder block.
+"""Drop-in classes for kungyao/vae-play's ``models/network_Style_GAN.py`` on the HIP back end: the Style-GAN generator and the
+blocks it is made of.
 
 Same constructor signatures and ``state_dict`` keys as the reference:
   ConvTranspose2d(in, out, 4, 2, 1)  nn.ConvTranspose2d with its default bias                    models/network_Style_GAN.py:49,116
      keys weight (in, out, 4, 4), bias (out); the bias is added in the scatter kernel's epilogue
   StyleUp(in_channel, out_channel)                                                               models/network_Style_GAN.py:45-65
      keys up_convs.0.{weight,bias}, cat_convs.0.conv.0.{weight,bias}, cat_convs.{1,2}.{cSE.1,cSE.3,sSE.0}.{weight,bias}
-The rest of the reference module (StyleEncoder, myConv2d, Generator, MLP, Discriminator) has no drop-in here yet;
-``blocks.Conv2d(in, out, 4, 2, bn="instance")`` is the convolution inside myConv2d (:95-98).
+  myConv2d(in, out, k, stride=1, bn=None, activate='relu')   conv_1(x) * (1 - label) + conv_2(x) * label      :72-79
+     keys conv_{1,2}.conv.0.weight[, bias]; one convolution with the two weights stacked along the output channel, then one
+     normalise-and-blend pass (functional.pair_blend); ``_PAIR_FUSED = False`` or a case the fused form does not cover
+     (bn="batch", a label that is not one number per image, a label that requires grad) runs the reference's expression
+  MLP(nf_in, nf_out, num_blocks)     keys model.{i}.fc.0.{weight,bias}, the reference's width rule                   :182-199
+  Generator(image_size, z_dim, max_channels=256)   encode / decode / forward(x, style_code, labels), 81 keys         :81-180
+StyleEncoder and Discriminator have no drop-in here yet.
 """
 from __future__ import annotations
 
@@ -17,7 +22,10 @@ import torch
 import torch.nn as nn
 
 from . import functional as F_hip
-from .blocks import Conv2d, SCSEBlock, _NoParams
+from .blocks import _CONV_LRELU, Conv2d, Linear, SCSEBlock, _NoParams, _act_name
+
+IMAGE_CHANNEL = 3
+_PAIR_FUSED = True           # myConv2d as one stacked convolution + functional.pair_blend; False: the reference's expression (A/B runs)
 
 
 class ConvTranspose2d(nn.Module):
@@ -58,3 +66,105 @@ class StyleUp(nn.Module):
         x = self.cat_convs[0](x)
         x = self.cat_convs[1](x)
         return self.cat_convs[2](x, relu=True)
+
+
+class myConv2d(nn.Module):
+    """models/network_Style_GAN.py:72-79: two independent Conv2d blocks on the same input, blended per image by ``label``.  The
+    blocks are held as ``conv_1`` / ``conv_2`` (the reference's keys and seeded init); the fused forward reads their parameters."""
+
+    def __init__(self, in_channel, out_channel, kernel_size, stride=1, bn=None, activate='relu'):
+        super().__init__()
+        self.conv_1 = Conv2d(in_channel, out_channel, kernel_size, stride, bn, activate)
+        self.conv_2 = Conv2d(in_channel, out_channel, kernel_size, stride, bn, activate)
+        self.stride, self.bn, self.act = stride, bn, _act_name(activate)
+
+    def uses_fused(self, x, label) -> bool:
+        """Does forward(x, label) take the stacked convolution + pair_blend?  One label per image (shape (B,) or (B, 1, ..., 1)),
+        no gradient asked for the label, bn None or "instance", and the module-level switch on."""
+        B = x.shape[0]
+        per_image = label.dim() >= 1 and label.shape[0] == B and label.numel() == B
+        return bool(_PAIR_FUSED and self.bn in (None, "instance") and per_image and not label.requires_grad)
+
+    def forward(self, x, label):
+        if not self.uses_fused(x, label):
+            return self.conv_1(x) * (1 - label) + self.conv_2(x) * label
+        p1, p2 = self.conv_1.conv[0], self.conv_2.conv[0]
+        bias = None if p1.bias is None else torch.cat([p1.bias, p2.bias])
+        u = F_hip.conv2d(x, torch.cat([p1.weight, p2.weight]), bias, self.stride)
+        return F_hip.pair_blend(u, label, self.bn == "instance", 1e-5, self.act, _CONV_LRELU)
+
+
+class MLP(nn.Module):
+    """models/network_Style_GAN.py:182-199: ``num_blocks`` Linear layers without activation, widths nf_in -> nf_in -> ... -> nf_out
+    growing by the reference's integer ratio."""
+
+    def __init__(self, nf_in, nf_out, num_blocks):
+        super().__init__()
+        self.model = nn.Sequential(*[Linear(i, o, activate=None) for i, o in self.widths(nf_in, nf_out, num_blocks)])
+
+    @staticmethod
+    def widths(nf_in, nf_out, num_blocks):
+        """(in, out) of every layer by the reference's rule, its truncations included"""
+        dims = [(nf_in, nf_in)]
+        out_dim = nf_in
+        ratio = int(2 ** (int(math.log2(nf_out / nf_in)) / (num_blocks - 1)))
+        for _ in range(num_blocks - 2):
+            in_dim = out_dim
+            out_dim = min(in_dim * ratio, nf_out)
+            dims.append((in_dim, out_dim))
+        dims.append((out_dim, nf_out))
+        return dims
+
+    def forward(self, x):
+        return self.model(x.reshape(x.size(0), -1))
+
+
+class Generator(nn.Module):
+    """models/network_Style_GAN.py:81-180: the style code becomes a fourth image channel through ``mlp``; six label-gated
+    convolutions encode, three StyleUp blocks decode against Conv2d(3) + InstanceNorm skips, ``final`` ends in tanh.  Modules are
+    created in the reference's order, so keys, their order and the seeded default init equal its."""
+
+    def __init__(self, image_size, z_dim, max_channels=256):
+        super().__init__()
+        self.z_dim = z_dim
+        self.image_size = image_size
+        self.conv1 = myConv2d(IMAGE_CHANNEL + 1, 32, 3, 1, activate=None)
+        self.conv2 = myConv2d(32, 32, 3, 1, activate=None)
+        self.down1 = myConv2d(32, 64, 4, 2, bn="instance")
+        self.down2 = myConv2d(64, 128, 4, 2, bn="instance")
+        self.down3 = myConv2d(128, 256, 4, 2, bn="instance")
+        self.down4 = myConv2d(256, 256, 4, 2, bn="instance")
+        self.up1 = StyleUp(256, 256)
+        self.up2 = StyleUp(256, 128)
+        self.up3 = StyleUp(128, 64)
+        self.skip1 = Conv2d(256, 256, 3, 1, bn="instance")
+        self.skip2 = Conv2d(128, 128, 3, 1, bn="instance")
+        self.skip3 = Conv2d(64, 64, 3, 1, bn="instance")
+        self.final = nn.Sequential(ConvTranspose2d(64, 32, 4, 2, 1), Conv2d(32, 32, 3, 1, bn=None), Conv2d(32, 32, 3, 1, bn=None),
+                                   Conv2d(32, IMAGE_CHANNEL, 3, 1, bn=None, activate=None), _NoParams())
+        self.mlp = MLP(z_dim, image_size * image_size, 3)
+
+    def encode(self, x, style_code, labels):
+        style_code = self.mlp(style_code)
+        style_code = style_code.reshape(style_code.size(0), 1, self.image_size, self.image_size)
+        x = torch.cat([x, style_code], dim=1)
+        labels = labels.reshape(labels.size(0), 1, 1, 1)
+        x = self.conv2(self.conv1(x, labels), labels)
+        d1 = self.down1(x, labels)
+        d2 = self.down2(d1, labels)
+        d3 = self.down3(d2, labels)
+        d4 = self.down4(d3, labels)
+        return x, d1, d2, d3, d4
+
+    def decode(self, c0, d1, d2, d3, d4, style_code):
+        up1 = self.up1(d4, self.skip1(d3))
+        up2 = self.up2(up1, self.skip2(d2))
+        up3 = self.up3(up2, self.skip3(d1))
+        x = up3
+        for m in list(self.final)[:4]:
+            x = m(x)
+        return F_hip.activation(x, "tanh")
+
+    def forward(self, x, style_code, labels):
+        c0, d1, d2, d3, d4 = self.encode(x, style_code, labels)
+        return self.decode(c0, d1, d2, d3, d4, style_code)

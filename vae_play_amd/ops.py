@@ -334,6 +334,37 @@ def instnorm_act_bwd(x, dy, mean, rstd, act: int, slope: float = 0.0, want_split
     return dx
 
 
+def pair_blend_fwd(u, label, norm: bool, eps: float, act: int, slope: float = 0.0, want_split: bool = False):
+    """u: (B, 2C, H, W) channels_last, the stacked convolution of a label-gated pair; label: (B,) float32 ->
+    (y (B, C, H, W), mean[B][2C] | None, rstd[B][2C] | None, the bf16 hi/lo planes of y | None)."""
+    B, C2, H, W = u.shape
+    assert _is_nhwc(u) and C2 % 2 == 0 and label.shape == (B,)
+    C = C2 // 2
+    y = empty_cl(B, C, H, W, u)
+    mean = rstd = ws = None
+    if norm:
+        mean = torch.empty((B, C2), dtype=torch.float32, device=u.device)
+        rstd = torch.empty((B, C2), dtype=torch.float32, device=u.device)
+        ws = _ws(_lib.load().vp_pair_blend_workspace_bytes(B, H * W, C), u)
+    ys = empty_split(y.numel(), u) if want_split else None
+    _lib.call("vp_pair_blend_fwd_f32", _p(u), _p(label), _p(y), _pv(ys), _p(mean), _p(rstd), B, H * W, C, int(norm), float(eps), act,
+              float(slope), _p(ws), 0 if ws is None else ws.numel() * 4, _stream())
+    return y, mean, rstd, ys
+
+
+def pair_blend_bwd(u, dy, label, mean, rstd, norm: bool, act: int, slope: float = 0.0, want_split: bool = False):
+    """Gradient of pair_blend_fwd with respect to u (the label is a constant): (du, the bf16 hi/lo planes of du | None)."""
+    B, C2, H, W = u.shape
+    C = C2 // 2
+    assert _is_nhwc(u) and _is_nhwc(dy) and tuple(dy.shape) == (B, C, H, W)
+    du = torch.empty_like(u)
+    ws = _ws(_lib.load().vp_pair_blend_workspace_bytes(B, H * W, C), u) if norm else None
+    dus = empty_split(u.numel(), u) if want_split else None
+    _lib.call("vp_pair_blend_bwd_f32", _p(u), _p(dy), _p(label), _p(mean), _p(rstd), _p(du), _pv(dus), B, H * W, C, int(norm), act,
+              float(slope), _p(ws), 0 if ws is None else ws.numel() * 4, _stream())
+    return du, dus
+
+
 def act_fwd(x, act: int, slope: float = 0.0):
     y = torch.empty_like(x)
     _lib.call("vp_act_fwd_f32", _p(x), _p(y), x.numel(), act, float(slope), _stream())

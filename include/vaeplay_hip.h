@@ -506,6 +506,24 @@ int vp_scse_bwd_f32(const float* x, const float* dy, const float* w1, const floa
                     float* db2, float* dw_s, float* db_s, int B, int HW, int C, int hidden, int relu, void* ws,
                     size_t ws_bytes, vp_stream stream);
 
+/* ---- the Style-GAN discriminator's output stage (models/network_Style_GAN.py:214-229), fp32, forward and backward ------------------
+ * Two 3x3 stride-2 padding-1 convolutions C -> 1 and C -> K on 2 x 2 maps, then sigmoid and softmax.  Only the taps (i+1, j+1),
+ * i, j in {0, 1}, meet data, so per image
+ *   adv[b]    = sigmoid(b_adv    + sum_{c,i,j} h_adv[b, 2i+j, c] * w_adv[0, c, i+1, j+1])                       adv [B][1]
+ *   aux[b, :] = softmax(b_aux[k] + sum_{c,i,j} h_aux[b, 2i+j, c] * w_aux[k, c, i+1, j+1])  (maximum subtracted)  aux [B][K]
+ * h_adv, h_aux: NHWC storage [B][4][C] of the two (B, C, 2, 2) inputs; w_adv (1, C, 3, 3), w_aux (K, C, 3, 3), b_adv [1], b_aux [K] as
+ * nn.Conv2d stores them (nothing is packed or copied).  Backward takes adv / aux as the forward call left them and writes (never
+ * accumulates) dh_adv, dh_aux [B][4][C], dw_adv (1, C, 3, 3), dw_aux (K, C, 3, 3) with row 0 and column 0 of every 3x3 as 0.0f, db_adv
+ * [1], db_aux [K].  d_adv [B][1] or d_aux [B][K] may be null: a zero gradient for that output.  Sums run in a fixed order without
+ * atomics (bit-reproducible), in fp32 whatever the convolution precision.  One launch per call, no workspace.
+ * Supported: B >= 1, 1 <= C <= 1024, 1 <= K <= 64; anything else, or a null required pointer, is refused with VP_ERR_ARG.  16-byte
+ * accesses to h / dh when C % 4 == 0 and those pointers are 16-byte aligned, scalar accesses otherwise (same range). */
+int vp_twin_head_fwd_f32(const float* h_adv, const float* h_aux, const float* w_adv, const float* b_adv, const float* w_aux,
+                         const float* b_aux, float* adv, float* aux, int B, int C, int K, vp_stream stream);
+int vp_twin_head_bwd_f32(const float* h_adv, const float* h_aux, const float* w_adv, const float* w_aux, const float* adv,
+                         const float* aux, const float* d_adv, const float* d_aux, float* dh_adv, float* dh_aux, float* dw_adv,
+                         float* db_adv, float* dw_aux, float* db_aux, int B, int C, int K, vp_stream stream);
+
 /* ---- optimiser step on a flat arena (train_BE.py:62-64,131; train.py:136-140) --------------- */
 /* torch.optim.Adam semantics (no amsgrad, no weight decay); g is multiplied by grad_scale first
  * (1/world_size after a sum all-reduce). step is the 1-based step count. */

@@ -8,6 +8,7 @@ Reference ops replaced (relative to the reference checkout):
   batch_norm_act     nn.BatchNorm2d/1d + F.relu (+ blocks acts) models/networks.py:16,28-29,66-67; models/blocks.py:19-30
   conv_transpose2d   nn.ConvTranspose2d(k4,s2,p1) + bias          models/network_Style_GAN.py:49,116
   pair_blend         myConv2d: norm + act + label blend of a stacked conv   models/network_Style_GAN.py:72-79
+  twin_head          Discriminator's two output convs + sigmoid / softmax   models/network_Style_GAN.py:214-229
   linear             nn.Linear                                  models/networks.py:65,69-70,88
   reparameterize     VaeGan.reparameterize                      models/networks.py:228-231
   kl_divergence      VaeGan.loss (kl term)                      models/networks.py:270
@@ -565,6 +566,8 @@ class _Act(Function):
 
     @staticmethod
     def forward(ctx, x, act: int, slope: float):
+        if x.dim() != 4:
+            x = x.contiguous()      # (a view with gaps, e.g. the flattened channel slice of a padded convolution output: the kernel walks dense memory)
         y = ops.act_fwd(x if (x.dim() != 4 or ops._is_nhwc(x)) else _cl(x), act, slope)
         ctx.act, ctx.slope = act, slope
         ctx.save_for_backward(y)
@@ -739,6 +742,45 @@ class _SCSE(Function):
         out = [_grad_out(p) if need[i + 1] else None for i, p in enumerate(ctx.params)]
         dx, *grads = ops.scse_bwd(x, _cl(dy), w1, w2, ws, pool, hid, cgate, sgate, ctx.relu, need_dx=need[0], out=out)
         return (dx, *(g if need[i + 1] else None for i, g in enumerate(grads)), None)
+
+
+class _TwinHead(Function):
+    """The Style-GAN discriminator's output stage (models/network_Style_GAN.py:214-229): the two last 3x3 stride-2 convolutions on
+    2 x 2 maps with their sigmoid and softmax, one launch forward and one backward; fp32 whatever ``set_conv_precision`` says
+    (1 + K dot products per image are nothing for an MFMA)."""
+
+    @staticmethod
+    def forward(ctx, h_adv, h_aux, w_adv, b_adv, w_aux, b_aux):
+        h_adv, h_aux = _cl(h_adv), _cl(h_aux)
+        ctx.set_materialize_grads(False)                   # an output the loss does not use arrives as None: a null d_adv / d_aux
+        adv, aux = ops.twin_head_fwd(h_adv, h_aux, w_adv, b_adv, w_aux, b_aux)
+        if any(ctx.needs_input_grad):
+            ctx.params = (w_adv, b_adv, w_aux, b_aux)      # the Parameters themselves: _grad_out looks for their arena slices
+            ctx.save_for_backward(h_adv, h_aux, w_adv, w_aux, adv, aux)
+        return adv, aux
+
+    @staticmethod
+    def backward(ctx, d_adv, d_aux):
+        h_adv, h_aux, w_adv, w_aux, adv, aux = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        out = [_grad_out(p) if need[i + 2] else None for i, p in enumerate(ctx.params)]
+        dh_adv, dh_aux, *grads = ops.twin_head_bwd(h_adv, h_aux, w_adv, w_aux, adv, aux, d_adv, d_aux, out=out)
+        return (dh_adv if need[0] else None, dh_aux if need[1] else None, *(g if need[i + 2] else None for i, g in enumerate(grads)))
+
+
+class _SoftmaxRows(Function):
+    """softmax over the last dimension of a 2-D tensor, on vp_softmax_rows_{fwd,bwd}_f32."""
+
+    @staticmethod
+    def forward(ctx, x):
+        y = ops.softmax_rows_fwd(x.contiguous())
+        ctx.save_for_backward(y)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (y,) = ctx.saved_tensors
+        return ops.softmax_rows_bwd(y, dy.contiguous())
 
 
 class _SelfAttention(Function):
@@ -966,6 +1008,20 @@ def scse(x, w1, b1, w2, b2, ws, bs, relu: bool = False):
     """SCSEBlock.forward (models/blocks.py:64-65) on the block's six parameters (cSE.1, cSE.3, sSE.0 weight and bias);
     ``relu=True`` also applies the ReLU that follows two of these blocks in StyleUp.cat_convs (models/network_Style_GAN.py:54-59)."""
     return _SCSE.apply(x, w1, b1, w2, b2, ws, bs, bool(relu))
+
+
+def twin_head(h_adv, h_aux, w_adv, b_adv, w_aux, b_aux):
+    """The Style-GAN discriminator's output stage (models/network_Style_GAN.py:214-229) on the (B, C, 2, 2) outputs of adv_convs.0 and
+    aux_convs.0: (adv_res (B, 1), aux_res (B, K)) = (sigmoid, softmax) of the 3x3 stride-2 convolutions with w_adv (1, C, 3, 3) and
+    w_aux (K, C, 3, 3), as one kernel forward and one backward."""
+    return _TwinHead.apply(h_adv, h_aux, w_adv, b_adv, w_aux, b_aux)
+
+
+def softmax_rows(x2d):
+    """``x2d.softmax(dim=-1)`` of a 2-D tensor."""
+    if x2d.dim() != 2:
+        raise ValueError("softmax_rows: a 2-D tensor is expected")
+    return _SoftmaxRows.apply(x2d)
 
 
 def self_attention(x, q, k, v, gamma):

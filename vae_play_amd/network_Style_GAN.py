@@ -1,5 +1,5 @@
 """Drop-in classes for kungyao/vae-play's ``models/network_Style_GAN.py`` on the HIP back end: the Style-GAN generator and the
-blocks it is made of.
+blocks it is made of, the style encoder and the discriminator.
 
 Same constructor signatures and ``state_dict`` keys as the reference:
   ConvTranspose2d(in, out, 4, 2, 1)  nn.ConvTranspose2d with its default bias                    models/network_Style_GAN.py:49,116
@@ -12,7 +12,13 @@ Same constructor signatures and ``state_dict`` keys as the reference:
      (bn="batch", a label that is not one number per image, a label that requires grad) runs the reference's expression
   MLP(nf_in, nf_out, num_blocks)     keys model.{i}.fc.0.{weight,bias}, the reference's width rule                   :182-199
   Generator(image_size, z_dim, max_channels=256)   encode / decode / forward(x, style_code, labels), 81 keys         :81-180
-StyleEncoder and Discriminator have no drop-in here yet.
+  StyleEncoder(z_dim, image_size, max_channels=1024)   forward(x) -> (mu, logvar)                                    :12-43
+     keys convs.0.conv.0.{weight,bias} (5x5), convs.{1..n}.conv.0.weight (3x3 stride 2 + InstanceNorm), two more stride-2 convs
+     with bias, fc_{mu,logvar}.fc.0.{weight,bias}
+  Discriminator(image_size, num_of_classes, max_channels=256)   forward(x, x_content, y) -> (adv_res, aux_res)       :201-229
+     keys convs.*, adv_convs.{0,1}.conv.0.{weight,bias}, aux_convs.{0,1}.conv.0.{weight,bias}; the two last convolutions with
+     their sigmoid and softmax run as one kernel (functional.twin_head) when they see 2 x 2 maps; ``_HEAD_FUSED = False`` or a
+     case the kernel does not cover runs the reference's expression
 """
 from __future__ import annotations
 
@@ -25,6 +31,8 @@ from . import functional as F_hip
 from .blocks import _CONV_LRELU, Conv2d, Linear, SCSEBlock, _NoParams, _act_name
 
 IMAGE_CHANNEL = 3
+_HEAD_FUSED = True           # Discriminator's output stage as functional.twin_head; False: the reference's expression (A/B runs)
+_HEAD_MAX_C, _HEAD_MAX_K = 1024, 64      # the range of vp_twin_head_*_f32 (include/vaeplay_hip.h)
 _PAIR_FUSED = True           # myConv2d as one stacked convolution + functional.pair_blend; False: the reference's expression (A/B runs)
 
 
@@ -168,3 +176,83 @@ class Generator(nn.Module):
     def forward(self, x, style_code, labels):
         c0, d1, d2, d3, d4 = self.encode(x, style_code, labels)
         return self.decode(c0, d1, d2, d3, d4, style_code)
+
+
+def _n_level(image_size):
+    return int(math.log2(image_size)) - 2
+
+
+def _flatten(x):
+    """``x.reshape(x.size(0), -1)`` of the logical NCHW tensor: a view where the NHWC memory already has that order (one channel
+    or one pixel), the HIP transpose otherwise"""
+    if x.shape[1] == 1 or x.shape[2] * x.shape[3] == 1:
+        return x.reshape(x.size(0), -1)
+    return F_hip.flatten_nchw(x)
+
+
+class StyleEncoder(nn.Module):
+    """models/network_Style_GAN.py:12-43: Conv2d(5) without activation, ``log2(image_size) - 2`` stride-2 Conv2d(3) + InstanceNorm +
+    ReLU that double the channels up to ``max_channels``, two more stride-2 Conv2d(3) + ReLU, then the two Linear heads on the
+    flattened map.  Modules are created in the reference's order, so keys, their order and the seeded default init equal its."""
+
+    def __init__(self, z_dim, image_size, max_channels=1024):
+        super().__init__()
+        in_dim, out_dim = IMAGE_CHANNEL, 64
+        convs = [Conv2d(in_dim, out_dim, 5, 1, activate=None)]
+        for _ in range(_n_level(image_size)):
+            in_dim, out_dim = out_dim, min(out_dim * 2, max_channels)
+            convs.append(Conv2d(in_dim, out_dim, 3, stride=2, bn="instance"))
+        convs.append(Conv2d(out_dim, out_dim, 3, stride=2))
+        convs.append(Conv2d(out_dim, out_dim, 3, stride=2))
+        self.convs = nn.Sequential(*convs)
+        self.fc_mu = Linear(out_dim, z_dim, activate=None)
+        self.fc_logvar = Linear(out_dim, z_dim, activate=None)
+
+    def forward(self, x):
+        x = _flatten(self.convs(x))
+        return self.fc_mu(x), self.fc_logvar(x)
+
+
+class Discriminator(nn.Module):
+    """models/network_Style_GAN.py:201-229: the image and the content image side by side through Conv2d(5) + ReLU and
+    ``log2(image_size) - 2`` stride-2 Conv2d(3) + InstanceNorm + ReLU, then two heads of two stride-2 Conv2d(3) each: one number
+    through a sigmoid, ``num_of_classes`` numbers through a softmax.  The first layer of each head stays a Conv2d block of its own;
+    the second layers, which see 2 x 2 maps at every power-of-two ``image_size``, run with their sigmoid and softmax as one
+    kernel (functional.twin_head).  Modules are created in the reference's order."""
+
+    def __init__(self, image_size, num_of_classes, max_channels=256):
+        super().__init__()
+        in_dim, out_dim = IMAGE_CHANNEL * 2, 64
+        convs = [Conv2d(in_dim, out_dim, 5, 1)]
+        for _ in range(_n_level(image_size)):
+            in_dim, out_dim = out_dim, min(out_dim * 2, max_channels)
+            convs.append(Conv2d(in_dim, out_dim, 3, stride=2, bn="instance"))
+        self.convs = nn.Sequential(*convs)
+        self.adv_convs = nn.Sequential(Conv2d(out_dim, out_dim, 3, stride=2, activate="lrelu"),
+                                       Conv2d(out_dim, 1, 3, stride=2, activate=None))
+        self.aux_convs = nn.Sequential(Conv2d(out_dim, out_dim, 3, stride=2, activate="lrelu"),
+                                       Conv2d(out_dim, num_of_classes, 3, stride=2, activate=None))
+        self.num_of_classes, self.head_channels = num_of_classes, out_dim
+
+    def _trunk_size(self, n):
+        for _ in range(len(self.convs) - 1):
+            n = (n - 1) // 2 + 1
+        return n
+
+    def uses_fused_head(self, x, x_content) -> bool:
+        """Does forward(x, x_content, y) take functional.twin_head?  The switch on, a 4 x 4 trunk output (so that the last layer
+        of each head sees 2 x 2), class and channel counts inside the kernel's range, fp32 tensors."""
+        return bool(_HEAD_FUSED and x.dim() == 4 and self._trunk_size(x.shape[2]) == 4 and self._trunk_size(x.shape[3]) == 4
+                    and 1 <= self.num_of_classes <= _HEAD_MAX_K and 1 <= self.head_channels <= _HEAD_MAX_C
+                    and x.dtype == torch.float32 and x_content.dtype == torch.float32
+                    and self.adv_convs[1].conv[0].weight.dtype == torch.float32)
+
+    def forward(self, x, x_content, y):
+        fused = self.uses_fused_head(x, x_content)
+        x = self.convs(torch.cat([x, x_content], dim=1))
+        if fused:
+            pa, pu = self.adv_convs[1].conv[0], self.aux_convs[1].conv[0]
+            return F_hip.twin_head(self.adv_convs[0](x), self.aux_convs[0](x), pa.weight, pa.bias, pu.weight, pu.bias)
+        adv_res = F_hip.activation(_flatten(self.adv_convs(x)), "sigmoid")
+        aux_res = F_hip.softmax_rows(_flatten(self.aux_convs(x)))
+        return adv_res, aux_res

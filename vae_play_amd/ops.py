@@ -489,6 +489,41 @@ def scse_bwd(x, dy, w1, w2, ws, pool, hid, cgate, sgate, relu: bool = False, nee
     return (dx, *grads)
 
 
+def twin_head_fwd(h_adv, h_aux, w_adv, b_adv, w_aux, b_aux):
+    """The Style-GAN discriminator's output stage on the channels_last (B, C, 2, 2) outputs of adv_convs.0 / aux_convs.0:
+    (adv (B, 1) = sigmoid, aux (B, K) = softmax) of the two 3x3 stride-2 convolutions, one launch.  w_adv (1, C, 3, 3),
+    w_aux (K, C, 3, 3) are the reference's conv weights."""
+    B, C, H, W = h_adv.shape
+    K = w_aux.shape[0]
+    assert (H, W) == (2, 2) and _is_nhwc(h_adv) and _is_nhwc(h_aux) and h_aux.shape == h_adv.shape
+    assert tuple(w_adv.shape) == (1, C, 3, 3) and tuple(w_aux.shape) == (K, C, 3, 3) and b_adv.numel() == 1 and b_aux.numel() == K
+    w_adv, b_adv, w_aux, b_aux = (t.contiguous() for t in (w_adv, b_adv, w_aux, b_aux))
+    adv = torch.empty((B, 1), dtype=torch.float32, device=h_adv.device)
+    aux = torch.empty((B, K), dtype=torch.float32, device=h_adv.device)
+    _lib.call("vp_twin_head_fwd_f32", _p(h_adv), _p(h_aux), _p(w_adv), _p(b_adv), _p(w_aux), _p(b_aux), _p(adv), _p(aux), B, C, K, _stream())
+    return adv, aux
+
+
+def twin_head_bwd(h_adv, h_aux, w_adv, w_aux, adv, aux, d_adv, d_aux, out=None):
+    """Gradients of twin_head_fwd: (dh_adv, dh_aux, dw_adv, db_adv, dw_aux, db_aux), one launch.  ``d_adv`` / ``d_aux`` may be None
+    (that output did not reach the loss); ``out`` may name, per parameter gradient, a contiguous tensor of the parameter's shape to
+    write into (None entries get a fresh tensor)."""
+    B, C, H, W = h_adv.shape
+    K = w_aux.shape[0]
+    assert (H, W) == (2, 2) and _is_nhwc(h_adv) and _is_nhwc(h_aux) and h_aux.shape == h_adv.shape
+    assert adv.is_contiguous() and aux.is_contiguous() and adv.numel() == B and tuple(aux.shape) == (B, K)
+    w_adv, w_aux = w_adv.contiguous(), w_aux.contiguous()
+    d_adv = None if d_adv is None else d_adv.contiguous()
+    d_aux = None if d_aux is None else d_aux.contiguous()
+    assert (d_adv is None or d_adv.numel() == B) and (d_aux is None or tuple(d_aux.shape) == (B, K))
+    dh_adv, dh_aux = torch.empty_like(h_adv), torch.empty_like(h_aux)
+    shapes = ((1, C, 3, 3), (1,), (K, C, 3, 3), (K,))
+    grads = [_out(o, shape, h_adv.device) for shape, o in zip(shapes, out or (None,) * 4)]
+    _lib.call("vp_twin_head_bwd_f32", _p(h_adv), _p(h_aux), _p(w_adv), _p(w_aux), _p(adv), _p(aux), _p(d_adv), _p(d_aux), _p(dh_adv),
+              _p(dh_aux), *(_p(g) for g in grads), B, C, K, _stream())
+    return (dh_adv, dh_aux, *grads)
+
+
 def softmax_rows_fwd(x2d):
     R, n = x2d.shape
     y = torch.empty_like(x2d)

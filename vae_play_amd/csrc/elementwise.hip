@@ -199,14 +199,19 @@ __global__ void __launch_bounds__(256) gan_head_kernel(const float* __restrict__
   __shared__ float sh[3][4];
   float acc[3] = {0.f, 0.f, 0.f};
   for (int i = threadIdx.x; i < 3 * B; i += 256) {
-    const float y = 1.f / (1.f + __expf(-logit[i]));
+    // y = sigmoid(x) and q = 1 - y = sigmoid(-x), each from e = exp(-|x|): "1.f - y" loses q once y rounds towards 1 (|q| error
+    // 6e-8 against the 1e-3 floor: 6e-5 of dlogit, and a saturated logit got gradient 0 instead of coef * 1e3 * q)
+    const float x = logit[i];
+    const float e = expf(-fabsf(x));
+    const float big = 1.f / (1.f + e), small = e / (1.f + e);
+    const float y = x >= 0.f ? big : small, q = x >= 0.f ? small : big;
     const int grp = i / B;
     float u, dldy;
     if (grp == 0) { u = y + 1e-3f; dldy = -1.f / u; }
-    else          { u = (1.f - y) + 1e-3f; dldy = 1.f / u; }
-    acc[grp] += -__logf(u);
+    else          { u = q + 1e-3f; dldy = 1.f / u; }
+    acc[grp] += -logf(u);
     if (p_out) p_out[i] = y;
-    if (dlogit) dlogit[i] = coef * dldy * y * (1.f - y);
+    if (dlogit) dlogit[i] = coef * dldy * y * q;
   }
 #pragma unroll
   for (int g = 0; g < 3; ++g) {

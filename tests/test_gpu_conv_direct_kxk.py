@@ -56,10 +56,10 @@ def _families(report, mode, x, y, w, stride, gather, scatter, dw, seed, bias=Non
 #             and edge heads, the discriminator's middle stages and the style encoder's) are listed once
 #   vaegan    VaeGan(128) at 16 images: the encoder's 5x5 convolutions, the decoder's last one and the discriminator's, which sees
 #             the 48 images of (x, x_tilde, x_p) in one pass (functional.conv5x5; the other rows run functional.conv2d)
-# Dispatch at these shapes: functional._ConvK sends 3x3 stride-1 layers with Cin <= 36, Cout <= 8 to the exact-fp32 small3 kernels in
+# Dispatch at these shapes: functional._Conv (family "conv2d") sends 3x3 stride-1 layers with Cin <= 36, Cout <= 8 to the exact-fp32 small3 kernels in
 # both modes (ids *_small3); in bf16x3 mode the other layers run on the split-bf16 kernels, zero-padded to a multiple of 8 on the side
 # whose channel count is not one (66 and 2 and 3 in, 1 out; ids *_padded), and in f32 mode on the exact-fp32 tile kernels.
-# functional._Conv5 in bf16x3 mode: the first encoder conv on its im2col as a 1x1 layer (and, its image requiring a gradient, the
+# functional._Conv (family "conv5x5") in bf16x3 mode: the first encoder conv on its im2col as a 1x1 layer (and, its image requiring a gradient, the
 # padded scatter), the decoder's 64 -> 1 on the edge kernels (vp_conv5_smallout_bf16x3 forward, vp_conv5_smallin_dgrad_bf16x3,
 # vp_conv5_smallout_wgrad_bf16x3), the discriminator's 1 -> 32 on vp_conv5_smallin_fwd_bf16x3 with its input gradient on the
 # flipped-tap vp_conv5_smallout_bf16x3; in f32 mode the narrow kernels.  The model runs these two edge layers with a sigmoid / ReLU
@@ -114,7 +114,7 @@ def _entry(row):
 
 
 def _small3(Cin, Cout, ks, stride, H, B):
-    """does functional._ConvK run this layer on the exact-fp32 small3 kernels (in both modes)?"""
+    """does functional._Conv run this layer on the exact-fp32 small3 kernels (in both modes)?"""
     from vae_play_amd import ops
     return ks == 3 and stride == 1 and ops.conv3_small_wgrad_applicable(B, H, H, Cin, Cout)
 
@@ -171,7 +171,7 @@ def test_front_end_layer_matches_the_direct_sum(row, layer, Cin, Cout, ks, strid
         assert tuple(y.shape) == (B, Cout, Hs, Hs)
         if feed == "split_planes" and Cout % 8 == 0:
             grads = []
-            y.register_hook(grads.append)               # the gradient object _ConvK / _Conv5.backward receives
+            y.register_hook(grads.append)               # the gradient object _Conv.backward receives
             _norm_act(row, y).backward(_nhwc(B, Cout, Hs, Hs, gen))
             dy = grads[0]
             assert getattr(dy, "_vp_split", None) is not None, "the normalisation's input gradient must carry split planes"
@@ -186,6 +186,34 @@ def test_front_end_layer_matches_the_direct_sum(row, layer, Cin, Cout, ks, strid
             _check(report, "dbias", "f32", b.grad[None], dy.double().sum((0, 2, 3))[None], dy.double().abs().sum((0, 2, 3))[None],
                    torch.full((1, Cout), B * Hs * Hs, device=DEV))
         print(f"direct-sum err/tau {row} {layer} {mode} {feed}: " + ", ".join(report))
+    finally:
+        FH.set_conv_precision(prev)
+
+
+@pytest.mark.parametrize("mode", ["f32", "bf16x3"])
+@pytest.mark.parametrize("H,W,stride", [(7, 9, 2), (7, 7, 1)], ids=["7x9-s2", "7x7-s1"])
+def test_conv5x5_on_an_odd_image_matches_the_direct_sum(H, W, stride, mode):
+    """functional.conv5x5, 8 -> 16 channels, on an image with odd sides: the output is floor((n + 4 - 5) / stride) + 1 wide, so with
+    stride 2 the big side is not twice the small one; y, dx and dW against the direct sums"""
+    from vae_play_amd import functional as FH
+    B, Cin, Cout = 2, 8, 16
+    seed = 97 * H + 13 * W + stride
+    gen = torch.Generator(device=DEV).manual_seed(seed)
+    prev = FH.get_conv_precision()
+    FH.set_conv_precision(mode)
+    try:
+        x = _nhwc(B, Cin, H, W, gen).requires_grad_(True)
+        w = (torch.randn(Cout, Cin, 5, 5, device=DEV, generator=gen) * (2.0 / (Cin * 25)) ** 0.5).requires_grad_(True)
+        y = FH.conv5x5(x, w, None, stride, None)
+        Hs, Ws = R.out_size(H, 5, stride), R.out_size(W, 5, stride)
+        assert tuple(y.shape) == (B, Cout, Hs, Ws)
+        dy = _nhwc(B, Cout, Hs, Ws, gen)
+        y.backward(dy)
+        torch.cuda.synchronize()
+        assert tuple(x.grad.shape) == (B, Cin, H, W)
+        report = []
+        _families(report, mode, x.detach(), dy, w.detach(), stride, y.detach(), x.grad, w.grad, seed)
+        print(f"direct-sum err/tau conv5x5 {H}x{W} stride {stride} {mode}: " + ", ".join(report))
     finally:
         FH.set_conv_precision(prev)
 

@@ -3,10 +3,11 @@ backward are HIP kernels (via ops.py -> C ABI).  This is what lets the reference
 ``loss.backward()`` idiom (train_BE.py:63) work unchanged on the drop-in modules.
 
 Reference ops replaced (relative to the reference checkout):
-  conv5x5            nn.Conv2d(k5,p2,stride)                    models/networks.py:14,100
-  conv_transpose5x5  nn.ConvTranspose2d(k5,s2,p2,op1)           models/networks.py:38
+  conv5x5            nn.Conv2d(k5,p2,stride)                    models/networks.py:14,100          (_Conv, family "conv5x5")
+  conv2d             nn.Conv2d(k in 1|3|4|5, p (k-1)//2, stride)  models/blocks.py:9-17            (_Conv, family "conv2d")
+  conv_transpose5x5  nn.ConvTranspose2d(k5,s2,p2,op1)           models/networks.py:38              (_ConvT)
   batch_norm_act     nn.BatchNorm2d/1d + F.relu (+ blocks acts) models/networks.py:16,28-29,66-67; models/blocks.py:19-30
-  conv_transpose2d   nn.ConvTranspose2d(k4,s2,p1) + bias          models/network_Style_GAN.py:49,116
+  conv_transpose2d   nn.ConvTranspose2d(k4,s2,p1) + bias          models/network_Style_GAN.py:49,116 (_ConvT)
   pair_blend         myConv2d: norm + act + label blend of a stacked conv   models/network_Style_GAN.py:72-79
   twin_head          Discriminator's two output convs + sigmoid / softmax   models/network_Style_GAN.py:214-229
   linear             nn.Linear                                  models/networks.py:65,69-70,88
@@ -16,6 +17,7 @@ Reference ops replaced (relative to the reference checkout):
 """
 from __future__ import annotations
 
+import collections
 import os
 import weakref
 
@@ -24,7 +26,7 @@ from typing import Optional
 import torch
 from torch.autograd import Function
 
-from . import _lib, ops
+from . import ops
 from .ops import ACT_CODES, ACT_NONE, ACT_SIGMOID
 
 
@@ -117,245 +119,246 @@ def _packed(fn, weight, want_p1: bool):
 _PACK_CACHE_ON = True
 
 
+def _smallin_shape(precision: str, Cout: int, Cin: int, stride: int) -> bool:
+    return precision == "bf16x3" and stride == 1 and Cin in (1, 3) and Cout in (32, 64)
+
+
 def first_conv_s1_edge(weight, stride: int) -> bool:
     """Does conv5x5(x, weight, bias, stride) run on the rows-in-K forward kernel (which takes a ReLU in its epilogue)?"""
-    return (_PRECISION == "bf16x3" and stride == 1 and weight.shape[1] in (1, 3) and weight.shape[0] in (32, 64))
+    return _smallin_shape(_PRECISION, weight.shape[0], weight.shape[1], stride)
 
 
-def _use16(weight) -> bool:
-    return _PRECISION == "bf16x3" and weight.shape[0] % 8 == 0 and weight.shape[1] % 8 == 0
+# ---- convolutions: route choice (pure functions of the geometry), one dense core, two Functions ---------------------------------
+_Route = collections.namedtuple("_Route", "fwd dx dw")       # the kernels of the forward pass, the input and the weight gradient
 
 
-class _Conv5(Function):
-    """small = act(bias + conv5x5(big)); weight (Csmall, Cbig, 5, 5) = nn.Conv2d layout."""
+def _conv_route(precision: str, small3: bool, small3_all: bool, family: str, Cout: int, Cin: int, ks: int, stride: int, act: int,
+                has_bias: bool, B: int, H: int, W: int) -> _Route:
+    """Which kernels run a convolution of the ``family`` "conv5x5" | "conv2d" (precision: get_conv_precision(); small3, small3_all:
+    the module flags; B, H, W: the input).  Names: "f32" / "x16" the dense core on exact-fp32 / split-bf16 operands (x16: both
+    channel counts multiples of 8), "padded" the split-bf16 core with the channel counts zero-padded to multiples of 8, "small3"
+    the few-channel VALU kernels, the others the 5x5 special cases for a 1- | 3-channel side.
+
+    The two families keep their own lists: conv2d never takes the 5x5 edge routes and conv5x5 never small3 / padded, as before
+    they shared a front end.  One list would move some shapes to other kernels (conv2d with ks = 5 on a 64 -> 1 layer would go to
+    the edge kernels): a performance change that needs measurements of its own."""
+    bf = precision == "bf16x3"
+    x16 = bf and Cout % 8 == 0 and Cin % 8 == 0
+    if family == "conv2d":
+        s3 = small3 and ks == 3 and stride == 1 and ops.conv3_small_wgrad_applicable(B, H, W, Cin, Cout)
+        if s3 and small3_all:
+            return _Route("small3", "small3", "small3")
+        base = "x16" if x16 else ("padded" if bf else "f32")
+        return _Route(base, base, "small3" if s3 else base)
+    if bf and stride == 2 and Cin in (1, 3) and Cout % 8 == 0 and act == ACT_NONE and not has_bias and H % 2 == 0 and W % 2 == 0:
+        return _Route("im2col", "scatter_padded", "im2col")
+    if _smallin_shape(precision, Cout, Cin, stride) and act in (ACT_NONE, ops.ACT_RELU):
+        return _Route("smallin", "smallout_flipped", "f32")
+    if x16 and act in (ACT_NONE, ACT_SIGMOID):
+        return _Route("x16", "x16", "x16")
+    smallout = bf and stride == 1 and Cin == 64 and Cout in (1, 3) and act in (ACT_NONE, ACT_SIGMOID)
+    if smallout:
+        dx = "smallin_dgrad"
+    elif bf and Cout < 8 and Cin % 8 == 0 and stride == 1:
+        dx = "halo_padded"
+    elif bf and Cin in (1, 3) and Cout in (32, 64) and stride == 1:
+        dx = "smallout_flipped"
+    elif bf and Cin < 8 and Cout % 8 == 0:
+        dx = "scatter_padded"
+    else:
+        dx = "f32"
+    dw = "smallout_wgrad" if smallout and ops.conv5_smallout_wgrad_bf16x3_workspace_bytes(B, H, W, Cin, Cout) else "f32"
+    return _Route("smallout" if smallout else "f32", dx, dw)
+
+
+def _convt_route(precision: str, Cin: int, Cout: int) -> str:
+    """Which dense core runs a transposed convolution: "x16" (split-bf16) | "f32"."""
+    return "x16" if precision == "bf16x3" and Cin % 8 == 0 and Cout % 8 == 0 else "f32"
+
+
+# The dense core: gather, scatter and weight gradient of a ks x ks, stride s layer with weight (Csmall, Cbig, ks, ks).  An operand is
+# the split planes of an activation (int16; the split-bf16 kernels) or the fp32 NHWC activation itself (the exact-fp32 kernels).
+def _is_split(t: torch.Tensor) -> bool:
+    return t.dtype == torch.int16
+
+
+def _gather(big, shape_big, weight, bias, stride: int, act: int = ACT_NONE):
+    """small = act(bias + conv(big))"""
+    ks = weight.shape[2]
+    if _is_split(big):
+        return ops.conv_gather_bf16x3(big, shape_big, _packed(ops.pack_w_split, weight, False), weight.shape[0], bias, ks, stride, act)
+    return ops.conv_gather(big, _packed(ops.pack_w, weight, False), bias, ks, stride, act)
+
+
+def _scatter(small, shape_small, weight, bias, stride: int, Hb: int, Wb: int):
+    """big (Hb x Wb) = bias + convT(small): a transposed convolution's forward pass, a convolution's input gradient"""
+    ks = weight.shape[2]
+    if _is_split(small):
+        return ops.conv_scatter_bias_bf16x3(small, shape_small, _packed(ops.pack_w_split, weight, True), bias, weight.shape[1], ks, stride,
+                                            Hb, Wb)
+    return ops.conv_scatter_bias(small, _packed(ops.pack_w, weight, True), bias, ks, stride, Hb, Wb)
+
+
+def _wgrad(big, shape_big, small, shape_small, ks: int, stride: int, param=None):
+    """dW (Csmall, Cbig, ks, ks), written into ``param``'s arena slice where _grad_out offers one"""
+    out = _grad_out(param)
+    if _is_split(big):
+        return ops.conv_wgrad_bf16x3(big, shape_big, small, shape_small, ks, stride, out=out)
+    return ops.conv_wgrad(big, small, ks, stride, out=out)
+
+
+def _bias_grad(dy, bias):
+    B, C, H, W = dy.shape
+    return ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * H * W, C), out=_grad_out(bias))
+
+
+def _pad8(c: int) -> int:
+    return (c + 7) // 8 * 8
+
+
+def _pad_w(weight, Cop: int, Cip: int):
+    Co, Ci = weight.shape[0], weight.shape[1]
+    return torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, Cip - Ci, 0, Cop - Co)) if (Cop != Co or Cip != Ci) else weight
+
+
+class _Conv(Function):
+    """small = act(bias + conv(big)): kernel k in {1,3,4,5}, stride 1|2, padding (k-1)//2; weight (Csmall, Cbig, k, k) = nn.Conv2d
+    layout.  ``family``: "conv5x5" (the VAE's layers, models/networks.py:14,100) | "conv2d" (models/blocks.py:9-17), see _conv_route."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride: int, act: int):
+    def forward(ctx, x, weight, bias, stride: int, act: int, family: str):
         x = _cl(x)
-        ctx.x16 = _use16(weight) and act in (ACT_NONE, ACT_SIGMOID)
-        ctx.cols = None
-        Cs, Cb = weight.shape[0], weight.shape[1]
-        if (_PRECISION == "bf16x3" and stride == 2 and Cb in (1, 3) and Cs % 8 == 0 and act == ACT_NONE and bias is None
-                and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0):
+        B, Ci, H, W = x.shape
+        Co = weight.shape[0]
+        r = _conv_route(_PRECISION, _SMALL3, _SMALL3_ALL, family, Co, Ci, weight.shape[2], stride, act, bias is not None, B, H, W)
+        a = x               # the operand the weight gradient reads
+        if r.fwd == "im2col":
             # first conv on a 1- / 3-channel image (models/networks.py:14 via :55): its im2col written once as split planes, then a
             # 1x1 layer on the split-bf16 kernels for the forward pass and the weight gradient (as the fused step does)
-            B, _, H, W = x.shape
-            KC = _lib.load().vp_im2col5s2_cols(Cb)
-            xcol = ops.empty_split(B * (H // 2) * (W // 2) * KC, x)
-            _lib.call("vp_im2col5s2_split_f32", ops._p(x), ops._pv(xcol), B, Cb, H, W, 0, ops._stream())
-            w0s = ops.empty_split(Cs * KC, x)
-            _lib.call("vp_pack_w_im2col5_split", ops._p(weight.contiguous()), ops._pv(w0s), Cs, Cb, ops._stream())
-            y = ops.conv_gather_bf16x3(xcol, (B, KC, H // 2, W // 2), w0s, Cs, None, 1, 1, ACT_NONE)
-            ctx.cols = (KC, B, H, W)
-            ctx.stride, ctx.act, ctx.has_bias = stride, act, False
-            ctx.save_for_backward(xcol, weight, None)
-            return y
-        if first_conv_s1_edge(weight, stride) and act in (ACT_NONE, ops.ACT_RELU):
+            a = ops.im2col5s2_split_f32(x)
+            y = ops.conv_gather_bf16x3(a, (B, ops.im2col5s2_cols(Ci), H // 2, W // 2), ops.pack_w_im2col5_split(weight), Co, None, 1, 1)
+        elif r.fwd == "smallin":
             # stride-1 first conv on a 1- / 3-channel image (the VAE-GAN discriminator's, models/networks.py:160-163) with bias and
             # ReLU in the epilogue: a kernel row of taps per MFMA k-step (csrc/edge.hip, the rows-in-K kernel's forward form)
-            B, _, H, W = x.shape
-            y = ops.empty_cl(B, Cs, H, W, x)
-            _lib.call("vp_conv5_smallin_fwd_bf16x3", ops._p(x), ops._p(weight.contiguous()), ops._p(bias), ops._p(y), B, H, W, Cb, Cs, act,
-                      ops._stream())
-            ctx.x16 = False
-            ctx.stride, ctx.act, ctx.has_bias = stride, act, bias is not None
-            ctx.bias_param = bias
-            ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
-            return y
-        if ctx.x16:
-            xs = _split_of(x)
-            p0 = _packed(ops.pack_w5_split, weight, False)
-            y = ops.conv5_gather_bf16x3(xs, x.shape, p0, weight.shape[0], bias, stride, act)
-            ctx.xshape = tuple(x.shape)
-            x = xs          # the split copy is what the weight gradient reads
-        else:
-            p0 = _packed(ops.pack_w5, weight, False)
+            y = ops.conv5_smallin_fwd_bf16x3(x, weight.contiguous(), bias, act)
+        elif r.fwd == "small3":
+            # a handful of channels on both sides (the networks_BE heads): one output pixel per thread, no packing / padding / split
+            # -- exact-fp32 VALU kernels (csrc/small3.hip) instead of a 64 x 64 MFMA tile that is 92 - 98 % padding
+            y = ops.conv3_small_fwd(x, weight.contiguous(), bias)
+        elif r.fwd == "padded":
+            # a channel count that is not a multiple of 8 on either side (32 + 2 coordinate channels in, 1 or 2 channels out):
+            # zero-pad it to the next multiple of 8 and stay on the split-bf16 kernels -- the exact-f32 tile kernels run these
+            # shapes with 70-97 % padding of their own (networks_BE heads: 65 % of the step in one f32 weight-gradient kernel)
+            Cop, Cip = _pad8(Co), _pad8(Ci)
+            bp = bias if (bias is None or Cop == Co) else torch.nn.functional.pad(bias, (0, Cop - Co))
+            a = ops.split_pad(x, Cip) if Cip != Ci else _split_of(x)
+            y = _gather(a, (B, Cip, H, W), _pad_w(weight, Cop, Cip), bp, stride)
+            y = y[:, :Co] if Cop != Co else y
+        elif r.fwd == "smallout":
             # the image side of the final conv (64 -> 1 | 3 channels, models/networks.py:100-103) on the matrix cores: the edge
             # kernels of the fused step (taps in the MFMA columns / rows, a kernel row per k-step) instead of the VALU kernels
-            ctx.edge = (_PRECISION == "bf16x3" and stride == 1 and weight.shape[1] == 64 and weight.shape[0] in (1, 3)
-                        and act in (ACT_NONE, ACT_SIGMOID))
-            if ctx.edge:
-                B, _, H, W = x.shape
-                y = ops.empty_cl(B, weight.shape[0], H, W, x)
-                _lib.call("vp_conv5_smallout_bf16x3", ops._p(x), ops._p(p0), ops._p(bias), ops._p(y), B, H, W, 64, weight.shape[0], act,
-                          ops._stream())
-            else:
-                y = ops.conv5_gather(x, p0, bias, stride, act)
-        ctx.stride, ctx.act, ctx.has_bias = stride, act, bias is not None
+            y = ops.conv5_smallout_bf16x3(x, _packed(ops.pack_w, weight, False), bias, act)
+        else:                   # "x16" | "f32"
+            a = _split_of(x) if r.fwd == "x16" else x
+            y = _gather(a, x.shape, weight, bias, stride, act)
+        ctx.route, ctx.stride, ctx.act, ctx.xshape = r, stride, act, tuple(x.shape)
         ctx.bias_param = bias
-        ctx.save_for_backward(x, weight, y if act != ACT_NONE else None)
+        ctx.save_for_backward(a, weight, y if act != ACT_NONE else None, x if r.dw == "small3" else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight, y = ctx.saved_tensors
+        a, weight, y, x32 = ctx.saved_tensors
+        r, stride = ctx.route, ctx.stride
+        need_dx, need_dw, need_db = ctx.needs_input_grad[:3]
         dy = _cl(dy)
         if ctx.act != ACT_NONE:
             dy = ops.act_bwd_from_y(y, dy, ctx.act)
+        B, Ci, H, W = ctx.xshape
+        Co, ks = weight.shape[0], weight.shape[2]
+        Cop, Cip = (_pad8(Co), _pad8(Ci)) if r.fwd == "padded" else (Co, Ci)
+        sshape = (B, Cop, dy.shape[2], dy.shape[3])
         dx = dw = db = None
-        if ctx.cols is not None:
-            KC, B, H, W = ctx.cols
-            Cs, Cb = weight.shape[0], weight.shape[1]
-            if ctx.needs_input_grad[1]:
-                dys = _split_of(dy)
-                dwc = ops.conv_wgrad_bf16x3(x, (B, KC, H // 2, W // 2), dys, tuple(dy.shape), 1, 1)      # [Cs][KC] in column order
-                dw = _grad_out(weight)
-                dw = dw if dw is not None else torch.empty_like(weight, memory_format=torch.contiguous_format)
-                _lib.call("vp_unpack_dw_im2col5_f32", ops._p(dwc), ops._p(dw), Cs, Cb, ops._stream())
-            if ctx.needs_input_grad[0]:           # (an image that requires a gradient: the padded split-bf16 scatter)
-                wpad = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, 8 - Cb))
-                _, p1 = ops.pack_w5_split(wpad, False, True)
-                dx = ops.conv5_scatter_bf16x3(ops.split_f32(dy), dy.shape, p1, 8, ctx.stride)[:, :Cb]
-            return dx, dw, None, None, None
-        if ctx.x16:
-            dys = _split_of(dy)
-            if ctx.needs_input_grad[0]:
-                p1 = _packed(ops.pack_w5_split, weight, True)
-                dx = ops.conv5_scatter_bf16x3(dys, dy.shape, p1, weight.shape[1], ctx.stride)
-            if ctx.needs_input_grad[1]:
-                dw = ops.conv5_wgrad_bf16x3(x, ctx.xshape, dys, tuple(dy.shape), ctx.stride, out=_grad_out(weight))
+        if need_dw and r.dw == "small3":
+            dw = ops.conv3_small_wgrad(x32, dy, out=_grad_out(weight))
+        if r.fwd == "padded":
+            dys = ops.split_pad(dy, Cop) if Cop != Co else _split_of(dy)
         else:
-            if ctx.needs_input_grad[0]:
-                Cs, Cb = weight.shape[0], weight.shape[1]
-                if getattr(ctx, "edge", False):
-                    B, _, H, W = dy.shape
-                    dx = ops.empty_cl(B, Cb, H, W, dy)
-                    _lib.call("vp_conv5_smallin_dgrad_bf16x3", ops._p(dy), ops._p(weight.contiguous()), ops._p(dx), B, H, W, Cs, Cb,
-                              ops._stream())
-                elif _PRECISION == "bf16x3" and Cs < 8 and Cb % 8 == 0 and ctx.stride == 1:
-                    # the image side of the final conv (1 or 3 channels): pad it to 8 channels and run the input gradient on
-                    # the split-bf16 halo kernel like the fused engine does (the exact-f32 scatter with K = 25 * Cs is a 94 %
-                    # padded MFMA tile: 494 us against ~60 us at 32 images of 128 x 128)
-                    B, _, H, W = dy.shape
-                    dyp = torch.zeros((B, H, W, 8), dtype=torch.float32, device=dy.device)
-                    dyp[..., :Cs] = dy.permute(0, 2, 3, 1)
-                    dx = ops.conv5_scatter_bf16x3(ops.split_f32(dyp), (B, 8, H, W), ops.pack_w5_p1_split_padded(weight, 8), Cb, 1)
-                elif (_PRECISION == "bf16x3" and Cb in (1, 3) and Cs in (32, 64) and ctx.stride == 1):
-                    # input gradient of a stride-1 first conv (the VAE-GAN discriminator's 1 -> 32, models/networks.py:160-163:
-                    # its input is the decoder's output): dx[p] = sum_{tap, co} dy[p - tap + 2][co] W[co][ci][tap] is the
-                    # "many channels -> 1 | 3" correlation of the tap-in-N kernel with the taps flipped
-                    B, _, H, W = dy.shape
-                    wf = weight.flip(2, 3).permute(1, 2, 3, 0).reshape(Cb, 25, Cs).contiguous()      # [ci][tap'][co]
-                    dx = ops.empty_cl(B, Cb, H, W, dy)
-                    _lib.call("vp_conv5_smallout_bf16x3", ops._p(dy), ops._p(wf), None, ops._p(dx), B, H, W, Cs, Cb, ACT_NONE, ops._stream())
-                elif _PRECISION == "bf16x3" and Cb < 8 and Cs % 8 == 0:
-                    # the image side of a FIRST conv whose input gradient is needed (the VAE-GAN discriminator's, models/
-                    # networks.py:160-163: its input is the decoder's output): zero-pad the weight's input channels to 8,
-                    # scatter on the split-bf16 kernels, keep the real channels.  The exact-f32 scatter to one output channel
-                    # pads the MFMA tile's 32 columns by 97 %: 522 us against 32 + 214 us at 48 images of 128 x 128
-                    # (tools/microbench_narrow_dgrad.py)
-                    wpad = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, 8 - Cb))
-                    _, p1 = ops.pack_w5_split(wpad, False, True)
-                    dx = ops.conv5_scatter_bf16x3(ops.split_f32(dy), dy.shape, p1, 8, ctx.stride)[:, :Cb]
-                else:
-                    p1 = _packed(ops.pack_w5, weight, True)
-                    dx = ops.conv5_scatter(dy, p1, ctx.stride)
-            if ctx.needs_input_grad[1]:
-                B, Cs, H, W = dy.shape
-                nb = (_lib.load().vp_conv5_smallout_wgrad_bf16x3_workspace_bytes(B, H, W, weight.shape[1], Cs)
-                      if getattr(ctx, "edge", False) else 0)
-                if nb:
-                    ws = torch.empty(nb // 4, dtype=torch.float32, device=dy.device)
-                    dw = _grad_out(weight)
-                    dw = dw if dw is not None else torch.empty_like(weight, memory_format=torch.contiguous_format)
-                    _lib.call("vp_conv5_smallout_wgrad_bf16x3", ops._p(x), ops._p(dy), ops._p(dw), B, H, W, weight.shape[1], Cs, ops._p(ws), nb,
-                              ops._stream())
-                else:
-                    dw = ops.conv5_wgrad(x, dy, ctx.stride, out=_grad_out(weight))
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            B, C, H, W = dy.shape
-            db = ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * H * W, C), out=_grad_out(ctx.bias_param))
-        return dx, dw, db, None, None
+            dys = _split_of(dy) if (r.fwd == "x16" or (need_dw and r.dw == "im2col")) else None
+        if need_dw and r.dw == "im2col":
+            dwc = _wgrad(a, (B, ops.im2col5s2_cols(Ci), H // 2, W // 2), dys, sshape, 1, 1)      # [Co][KC] in column order
+            dw = ops.unpack_dw_im2col5_f32(dwc, Ci, out=_grad_out(weight))
+        if need_dx:
+            if r.dx == "small3":
+                dx = ops.conv3_small_dgrad(dy, weight.contiguous())
+            elif r.dx == "smallin_dgrad":
+                dx = ops.conv5_smallin_dgrad_bf16x3(dy, weight.contiguous())
+            elif r.dx == "halo_padded":
+                # the image side of the final conv (1 or 3 channels): pad it to 8 channels and run the input gradient on
+                # the split-bf16 halo kernel like the fused engine does (the exact-f32 scatter with K = 25 * Cs is a 94 %
+                # padded MFMA tile: 494 us against ~60 us at 32 images of 128 x 128)
+                dyp = torch.zeros((B, H, W, 8), dtype=torch.float32, device=dy.device)
+                dyp[..., :Co] = dy.permute(0, 2, 3, 1)
+                dx = ops.conv_scatter_bf16x3(ops.split_f32(dyp), (B, 8, H, W), ops.pack_w5_p1_split_padded(weight, 8), Ci, 5, 1, H, W)
+            elif r.dx == "smallout_flipped":
+                # input gradient of a stride-1 first conv (the VAE-GAN discriminator's 1 -> 32, models/networks.py:160-163:
+                # its input is the decoder's output): dx[p] = sum_{tap, co} dy[p - tap + 2][co] W[co][ci][tap] is the
+                # "many channels -> 1 | 3" correlation of the tap-in-N kernel with the taps flipped
+                wf = weight.flip(2, 3).permute(1, 2, 3, 0).reshape(Ci, 25, Co).contiguous()      # [ci][tap'][co]
+                dx = ops.conv5_smallout_bf16x3(dy, wf, None, ACT_NONE)
+            elif r.dx == "scatter_padded":
+                # the image side of a FIRST conv whose input gradient is needed (the VAE-GAN discriminator's, models/
+                # networks.py:160-163: its input is the decoder's output): zero-pad the weight's input channels to 8,
+                # scatter on the split-bf16 kernels, keep the real channels.  The exact-f32 scatter to one output channel
+                # pads the MFMA tile's 32 columns by 97 %: 522 us against 32 + 214 us at 48 images of 128 x 128
+                # (tools/microbench_narrow_dgrad.py)
+                _, p1 = ops.pack_w_split(_pad_w(weight, Co, 8), False, True)
+                dx = ops.conv_scatter_bf16x3(ops.split_f32(dy), sshape, p1, 8, ks, stride, H, W)[:, :Ci]
+            else:               # "padded" | "x16" | "f32"
+                dx = _scatter(dy if r.dx == "f32" else dys, sshape, _pad_w(weight, Cop, Cip), None, stride, H, W)
+                dx = dx[:, :Ci] if Cip != Ci else dx
+        if need_dw and dw is None:
+            if r.dw == "smallout_wgrad":
+                dw = ops.conv5_smallout_wgrad_bf16x3(a, dy, out=_grad_out(weight))
+            elif r.dw == "padded":
+                dw = _wgrad(a, (B, Cip, H, W), dys, sshape, ks, stride)[:Co, :Ci].contiguous()
+            else:               # "x16" | "f32"
+                dw = _wgrad(a, ctx.xshape, dy if r.dw == "f32" else dys, sshape, ks, stride, weight)
+        if ctx.bias_param is not None and need_db:
+            db = _bias_grad(dy, ctx.bias_param)
+        return dx, dw, db, None, None, None
 
 
-class _ConvT5(Function):
-    """big = convT5x5(small), stride 2, padding 2, output_padding 1; weight (Csmall, Cbig, 5, 5)
-    = nn.ConvTranspose2d layout (in_channels first)."""
+class _ConvT(Function):
+    """big = bias + convT(small) with Hb = stride * Hs: kernel 5, padding 2, output_padding stride - 1 (models/networks.py:38) or
+    kernel 4, stride 2, padding 1 (models/network_Style_GAN.py:49,116); weight (Csmall, Cbig, k, k) = nn.ConvTranspose2d layout
+    (in_channels first).  The bias is added in the scatter kernel's epilogue."""
 
     @staticmethod
-    def forward(ctx, x, weight, stride: int):
-        x = _cl(x)
-        ctx.x16 = _use16(weight)
-        if ctx.x16:
-            xs = _split_of(x)
-            p1 = _packed(ops.pack_w5_split, weight, True)
-            y = ops.conv5_scatter_bf16x3(xs, x.shape, p1, weight.shape[1], stride)
-            ctx.xshape = tuple(x.shape)
-            x = xs
-        else:
-            p1 = _packed(ops.pack_w5, weight, True)
-            y = ops.conv5_scatter(x, p1, stride)
-        ctx.stride = stride
-        ctx.save_for_backward(x, weight)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
-        dy = _cl(dy)
-        dx = dw = None
-        if ctx.x16:
-            dys = _split_of(dy)
-            if ctx.needs_input_grad[0]:
-                p0 = _packed(ops.pack_w5_split, weight, False)
-                dx = ops.conv5_gather_bf16x3(dys, dy.shape, p0, weight.shape[0], None, ctx.stride, ACT_NONE)
-            if ctx.needs_input_grad[1]:
-                dw = ops.conv5_wgrad_bf16x3(dys, tuple(dy.shape), x, ctx.xshape, ctx.stride, out=_grad_out(weight))
-            return dx, dw, None
-        if ctx.needs_input_grad[0]:
-            p0 = _packed(ops.pack_w5, weight, False)
-            dx = ops.conv5_gather(dy, p0, None, ctx.stride, ACT_NONE)
-        if ctx.needs_input_grad[1]:
-            dw = ops.conv5_wgrad(dy, x, ctx.stride, out=_grad_out(weight))
-        return dx, dw, None
-
-
-class _ConvT4(Function):
-    """big = bias + convT4x4(small), stride 2, padding 1 (Hb = 2 Hs); weight (Csmall, Cbig, 4, 4) = nn.ConvTranspose2d layout
-    (models/network_Style_GAN.py:49,116).  The bias is added in the scatter kernel's epilogue."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, stride: int):
         x = _cl(x)
         B, Cs, Hs, Ws = x.shape
-        Cb = weight.shape[1]
-        ctx.x16 = _use16(weight)
-        ctx.xshape = tuple(x.shape)
-        if ctx.x16:
-            xs = _split_of(x)
-            p1 = _packed(ops.pack_w_split, weight, True)
-            y = ops.conv_scatter_bias_bf16x3(xs, x.shape, p1, bias, Cb, 4, 2, 2 * Hs, 2 * Ws)
-            x = xs          # the split copy is what the weight gradient reads
-        else:
-            p1 = _packed(ops.pack_w, weight, True)
-            y = ops.conv_scatter_bias(x, p1, bias, 4, 2, 2 * Hs, 2 * Ws)
-        ctx.has_bias = bias is not None
+        ctx.route = _convt_route(_PRECISION, Cs, weight.shape[1])
+        a = _split_of(x) if ctx.route == "x16" else x          # the split copy is what the weight gradient reads
+        y = _scatter(a, x.shape, weight, bias, stride, Hs * stride, Ws * stride)
+        ctx.stride, ctx.xshape = stride, tuple(x.shape)
         ctx.bias_param = bias
-        ctx.save_for_backward(x, weight)
+        ctx.save_for_backward(a, weight)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, weight = ctx.saved_tensors
+        a, weight = ctx.saved_tensors
         dy = _cl(dy)
         dx = dw = db = None
-        if ctx.x16:
-            dys = _split_of(dy)
-            if ctx.needs_input_grad[0]:
-                p0 = _packed(ops.pack_w_split, weight, False)
-                dx = ops.conv_gather_bf16x3(dys, dy.shape, p0, weight.shape[0], None, 4, 2, ACT_NONE)
-            if ctx.needs_input_grad[1]:
-                dw = ops.conv_wgrad_bf16x3(dys, tuple(dy.shape), x, ctx.xshape, 4, 2, out=_grad_out(weight))
-        else:
-            if ctx.needs_input_grad[0]:
-                p0 = _packed(ops.pack_w, weight, False)
-                dx = ops.conv_gather(dy, p0, None, 4, 2, ACT_NONE)
-            if ctx.needs_input_grad[1]:
-                dw = ops.conv_wgrad(dy, x, 4, 2, out=_grad_out(weight))
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            B, C, H, W = dy.shape
-            db = ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * H * W, C), out=_grad_out(ctx.bias_param))
-        return dx, dw, db
+        dys = _split_of(dy) if ctx.route == "x16" else dy
+        if ctx.needs_input_grad[0]:
+            dx = _gather(dys, dy.shape, weight, None, ctx.stride)
+        if ctx.needs_input_grad[1]:
+            dw = _wgrad(dys, tuple(dy.shape), a, ctx.xshape, weight.shape[2], ctx.stride, weight)
+        if ctx.bias_param is not None and ctx.needs_input_grad[2]:
+            db = _bias_grad(dy, ctx.bias_param)
+        return dx, dw, db, None
 
 
 class _BatchNormAct(Function):
@@ -452,113 +455,6 @@ class _UnflattenNCHW(Function):
     def backward(ctx, dy):
         dy = _cl(dy)
         return ops.nhwc_to_nchw(dy).reshape(dy.shape[0], -1), None, None, None
-
-
-class _ConvK(Function):
-    """nn.Conv2d(kernel k in {1,3,4,5}, stride 1|2, padding (k-1)//2) -- models/blocks.py:9-17."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride: int):
-        x = _cl(x)
-        ks = weight.shape[2]
-        ctx.x16 = _use16(weight)
-        ctx.xshape = tuple(x.shape)
-        ctx.pad = None
-        Co, Ci = weight.shape[0], weight.shape[1]
-        # a handful of channels on both sides (the networks_BE heads): the weight gradient is a reduction over the pixels into a few
-        # hundred numbers -- exact-fp32 VALU kernel (csrc/small3.hip) instead of a 64 x 64 MFMA tile that is 92 - 98 % padding
-        ctx.small3 = (_SMALL3 and ks == 3 and stride == 1 and x.dtype == torch.float32
-                      and ops.conv3_small_wgrad_applicable(x.shape[0], x.shape[2], x.shape[3], Ci, Co))
-        x32 = x if ctx.small3 else None
-        ctx.direct3 = ctx.small3 and _SMALL3_ALL
-        if ctx.direct3:                 # forward and input gradient too: one output pixel per thread, no packing / padding / split
-            y = ops.conv3_small_fwd(x, weight.contiguous(), bias)
-            ctx.stride, ctx.ks, ctx.has_bias = stride, ks, bias is not None
-            ctx.bias_param = bias
-            ctx.save_for_backward(x, weight, x32)
-            return y
-        if _PRECISION == "bf16x3" and not ctx.x16:
-            # a channel count that is not a multiple of 8 on either side (32 + 2 coordinate channels in, 1 or 2 channels out):
-            # zero-pad it to the next multiple of 8 and stay on the split-bf16 kernels -- the exact-f32 tile kernels run these
-            # shapes with 70-97 % padding of their own (networks_BE heads: 65 % of the step in one f32 weight-gradient kernel)
-            Cop, Cip = (Co + 7) // 8 * 8, (Ci + 7) // 8 * 8
-            wp = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, Cip - Ci, 0, Cop - Co)) if (Cop != Co or Cip != Ci) else weight
-            bp = None if bias is None else (torch.nn.functional.pad(bias, (0, Cop - Co)) if Cop != Co else bias)
-            xs = ops.split_pad(x, Cip) if Cip != Ci else _split_of(x)
-            B, _, H, W = x.shape
-            p0, _ = ops.pack_w_split(wp, True, False)
-            y = ops.conv_gather_bf16x3(xs, (B, Cip, H, W), p0, Cop, bp, ks, stride, ACT_NONE)
-            ctx.pad = (Co, Ci, Cop, Cip)
-            ctx.stride, ctx.ks, ctx.has_bias = stride, ks, bias is not None
-            ctx.bias_param = bias
-            ctx.save_for_backward(xs, weight, x32)
-            return y[:, :Co] if Cop != Co else y
-        if ctx.x16:                     # split-bf16 kernels (set_conv_precision("bf16x3"), channel counts multiples of 8)
-            xs = _split_of(x)
-            p0 = _packed(ops.pack_w_split, weight, False)
-            y = ops.conv_gather_bf16x3(xs, x.shape, p0, weight.shape[0], bias, ks, stride, ACT_NONE)
-            x = xs
-        else:
-            p0 = _packed(ops.pack_w, weight, False)
-            y = ops.conv_gather(x, p0, bias, ks, stride, ACT_NONE)
-        ctx.stride, ctx.ks, ctx.has_bias = stride, ks, bias is not None
-        ctx.bias_param = bias
-        ctx.save_for_backward(x, weight, x32)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, weight, x32 = ctx.saved_tensors
-        dy = _cl(dy)
-        dx = dw = db = None
-        small_dw = None
-        if ctx.small3 and ctx.needs_input_grad[1]:
-            small_dw = ops.conv3_small_wgrad(x32, dy, out=_grad_out(weight))
-        if ctx.direct3:
-            if ctx.needs_input_grad[0]:
-                dx = ops.conv3_small_dgrad(dy, weight.contiguous())
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                B, C, H, W = dy.shape
-                db = ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * H * W, C), out=_grad_out(ctx.bias_param))
-            return dx, small_dw, db, None
-        if ctx.pad is not None:
-            Co, Ci, Cop, Cip = ctx.pad
-            B, _, Ho, Wo = dy.shape
-            dys = ops.split_pad(dy, Cop) if Cop != Co else _split_of(dy)
-            if ctx.needs_input_grad[0]:
-                wp = torch.nn.functional.pad(weight, (0, 0, 0, 0, 0, Cip - Ci, 0, Cop - Co)) if (Cop != Co or Cip != Ci) else weight
-                _, p1 = ops.pack_w_split(wp, False, True)
-                dx = ops.conv_scatter_bf16x3(dys, (B, Cop, Ho, Wo), p1, Cip, ctx.ks, ctx.stride, ctx.xshape[2], ctx.xshape[3])
-                dx = dx[:, :Ci] if Cip != Ci else dx
-            if small_dw is not None:
-                dw = small_dw
-            elif ctx.needs_input_grad[1]:
-                dw = ops.conv_wgrad_bf16x3(x, (B, Cip, ctx.xshape[2], ctx.xshape[3]), dys, (B, Cop, Ho, Wo), ctx.ks, ctx.stride)
-                dw = dw[:Co, :Ci].contiguous() if (Cop != Co or Cip != Ci) else dw
-            if ctx.has_bias and ctx.needs_input_grad[2]:
-                db = ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * Ho * Wo, Co))
-            return dx, dw, db, None
-        if ctx.x16:
-            dys = _split_of(dy)
-            if ctx.needs_input_grad[0]:
-                p1 = _packed(ops.pack_w_split, weight, True)
-                dx = ops.conv_scatter_bf16x3(dys, dy.shape, p1, weight.shape[1], ctx.ks, ctx.stride, ctx.xshape[2], ctx.xshape[3])
-            if small_dw is not None:
-                dw = small_dw
-            elif ctx.needs_input_grad[1]:
-                dw = ops.conv_wgrad_bf16x3(x, ctx.xshape, dys, tuple(dy.shape), ctx.ks, ctx.stride, out=_grad_out(weight))
-        else:
-            if ctx.needs_input_grad[0]:
-                p1 = _packed(ops.pack_w, weight, True)
-                dx = ops.conv_scatter(dy, p1, ctx.ks, ctx.stride, x.shape[2], x.shape[3])
-            if small_dw is not None:
-                dw = small_dw
-            elif ctx.needs_input_grad[1]:
-                dw = ops.conv_wgrad(x, dy, ctx.ks, ctx.stride, out=_grad_out(weight))
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            B, C, H, W = dy.shape
-            db = ops.colsum(dy.permute(0, 2, 3, 1).reshape(B * H * W, C), out=_grad_out(ctx.bias_param))
-        return dx, dw, db, None
 
 
 class _Act(Function):
@@ -913,11 +809,13 @@ class _HalfSqDiff(Function):
 
 # ---- public functional API ----------------------------------------------------------------------
 def conv5x5(x, weight, bias=None, stride: int = 2, act: Optional[str] = None):
-    return _Conv5.apply(x, weight, bias, stride, ACT_CODES[act])
+    if tuple(weight.shape[2:]) != (5, 5):
+        raise ValueError("conv5x5 takes a (Cout, Cin, 5, 5) weight")
+    return _Conv.apply(x, weight, bias, stride, ACT_CODES[act], "conv5x5")
 
 
 def conv_transpose5x5(x, weight, stride: int = 2):
-    return _ConvT5.apply(x, weight, stride)
+    return _ConvT.apply(x, weight, None, stride)
 
 
 def batch_norm_act(x, gamma, beta, running_mean, running_var, training: bool, momentum: float = 0.1, eps: float = 1e-5,
@@ -931,14 +829,14 @@ def linear(x, weight, bias=None):
 
 def conv2d(x, weight, bias=None, stride: int = 1):
     """k x k convolution, k in {1,3,4,5}, padding (k-1)//2 (models/blocks.py Conv2d)."""
-    return _ConvK.apply(x, weight, bias, stride)
+    return _Conv.apply(x, weight, bias, stride, ACT_NONE, "conv2d")
 
 
 def conv_transpose2d(x, weight, bias=None, stride: int = 2):
     """nn.ConvTranspose2d(in, out, 4, 2, 1) (models/network_Style_GAN.py:49,116): weight (in, out, 4, 4), output 2H x 2W."""
     if weight.dim() != 4 or tuple(weight.shape[2:]) != (4, 4) or stride != 2:
         raise ValueError("HIP conv_transpose2d supports kernel_size 4, stride 2, padding 1")
-    return _ConvT4.apply(x, weight, bias)
+    return _ConvT.apply(x, weight, bias, stride)
 
 
 def activation(x, act: Optional[str], slope: float = 0.0):

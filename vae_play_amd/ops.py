@@ -747,6 +747,83 @@ def conv5_wgrad_bf16x3(big_split, shape_big, small_split, shape_small, stride: i
     return dw
 
 
+# ---- 5x5 layers with a 1- or 3-channel side: the edge kernels (csrc/edge.hip) and the first conv as a 1x1 layer over its im2col ----
+def conv5_smallin_fwd_bf16x3(x, weight, bias, act: int = ACT_NONE):
+    """act(bias + conv5x5 stride 1) of a 1- | 3-channel fp32 NHWC image; weight (Cout, Cin, 5, 5) in the reference layout."""
+    B, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    assert _is_nhwc(x) and weight.is_contiguous()
+    y = empty_cl(B, Cout, H, W, x)
+    _lib.call("vp_conv5_smallin_fwd_bf16x3", _p(x), _p(weight), _p(bias), _p(y), B, H, W, Cin, Cout, act, _stream())
+    return y
+
+
+def conv5_smallout_bf16x3(x, w_p0, bias, act: int = ACT_NONE):
+    """act(bias + conv5x5 stride 1) down to 1 | 3 channels; x fp32 NHWC, w_p0 [Cout][25][Cin] fp32."""
+    B, Cin, H, W = x.shape
+    Cout = w_p0.shape[0]
+    assert _is_nhwc(x) and w_p0.is_contiguous()
+    y = empty_cl(B, Cout, H, W, x)
+    _lib.call("vp_conv5_smallout_bf16x3", _p(x), _p(w_p0), _p(bias), _p(y), B, H, W, Cin, Cout, act, _stream())
+    return y
+
+
+def conv5_smallin_dgrad_bf16x3(dy, weight):
+    """input gradient of a stride-1 5x5 conv whose OUTPUT has 1 | 3 channels; dy fp32 NHWC, weight (Cout, Cin, 5, 5)."""
+    B, Cout, H, W = dy.shape
+    Cin = weight.shape[1]
+    assert _is_nhwc(dy) and weight.is_contiguous()
+    dx = empty_cl(B, Cin, H, W, dy)
+    _lib.call("vp_conv5_smallin_dgrad_bf16x3", _p(dy), _p(weight), _p(dx), B, H, W, Cout, Cin, _stream())
+    return dx
+
+
+def conv5_smallout_wgrad_bf16x3_workspace_bytes(B: int, H: int, W: int, Cin: int, Cout: int) -> int:
+    """0: the kernel does not take this shape"""
+    return _lib.load().vp_conv5_smallout_wgrad_bf16x3_workspace_bytes(B, H, W, Cin, Cout)
+
+
+def conv5_smallout_wgrad_bf16x3(x, dy, out: Optional[torch.Tensor] = None):
+    """dW (Cout, Cin, 5, 5) of a stride-1 5x5 conv down to 1 | 3 channels; x, dy fp32 NHWC."""
+    B, Cin, H, W = x.shape
+    Cout = dy.shape[1]
+    assert _is_nhwc(x) and _is_nhwc(dy)
+    ws = _ws(conv5_smallout_wgrad_bf16x3_workspace_bytes(B, H, W, Cin, Cout), x)
+    dw = _out(out, (Cout, Cin, 5, 5), x.device)
+    _lib.call("vp_conv5_smallout_wgrad_bf16x3", _p(x), _p(dy), _p(dw), B, H, W, Cin, Cout, _p(ws), ws.numel() * 4, _stream())
+    return dw
+
+
+def im2col5s2_cols(C: int) -> int:
+    """columns per output pixel of the 5x5 stride-2 im2col of a C-channel image (five kernel rows, padded)"""
+    return _lib.load().vp_im2col5s2_cols(C)
+
+
+def im2col5s2_split_f32(x, nchw: bool = False):
+    """split planes [B * H/2 * W/2][im2col5s2_cols(C)] of the 5x5 stride-2 patches of an image (NHWC, or NCHW with ``nchw``)"""
+    B, C, H, W = x.shape
+    out = empty_split(B * (H // 2) * (W // 2) * im2col5s2_cols(C), x)
+    _lib.call("vp_im2col5s2_split_f32", _p(x), _pv(out), B, C, H, W, int(nchw), _stream())
+    return out
+
+
+def pack_w_im2col5_split(weight):
+    """weight (Cout, C, 5, 5) -> split planes [Cout][im2col5s2_cols(C)] in the im2col column order"""
+    Cout, C = weight.shape[0], weight.shape[1]
+    weight = weight.contiguous()
+    out = empty_split(Cout * im2col5s2_cols(C), weight)
+    _lib.call("vp_pack_w_im2col5_split", _p(weight), _pv(out), Cout, C, _stream())
+    return out
+
+
+def unpack_dw_im2col5_f32(dwc, C: int, out: Optional[torch.Tensor] = None):
+    """dW in the im2col column order [Cout][im2col5s2_cols(C)] -> the reference layout (Cout, C, 5, 5)"""
+    Cout = dwc.shape[0]
+    dw = _out(out, (Cout, C, 5, 5), dwc.device)
+    _lib.call("vp_unpack_dw_im2col5_f32", _p(dwc), _p(dw), Cout, C, _stream())
+    return dw
+
+
 # ---- fp16-pair operands: products = 3 (~1e-6 relative) or 2 (two MFMAs per fragment pair, declared tolerance ~2e-4 per layer) ----
 def conv5_gather_f16(big_split, shape_big, w_p0_split, Cs: int, bias, stride: int, act: int = ACT_NONE, products: int = 2,
                      out_scale: float = 1.0):

@@ -115,7 +115,7 @@ def _check_epilogue_statistics(name, x, p0, p1, y, Cb, Cs, Hs, B, cx, precision=
         # launch runs the very kernel of the plain launch -- f32_fast_gather / f32_fast_scatter resp. gather16_t / scatter16_t on the
         # same problem type, tile and split rule, the statistics pointer is a kernel argument -- so the outputs must be equal bit for bit.
         # bf16x3, round 3: a plain launch may take ANOTHER kernel than the statistics launch of the same shape -- the pipelined kernel
-        # on the v_mfma_f32_16x16x32_bf16 form (conv16_impl.h plan16: the gather shapes with 256 output columns and 16 K - 64 K rows),
+        # on the v_mfma_f32_16x16x32_bf16 form (launch_plan.h plan_conv: the gather shapes with 256 output columns and 16 K - 64 K rows),
         # whose accumulator layout the epilogue does not read -- and that form equals the 32x32x16 kernels to rounding, not bit for
         # bit: the outputs must then agree to 2e-6 of their RMS.
         if precision != "bf16x3":

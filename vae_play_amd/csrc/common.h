@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include "../../include/vaeplay_hip.h"
 #include "env.h"
+#include "launch_plan.h"
 
 namespace vp {
 
@@ -32,6 +33,24 @@ inline int check_launch(const char* what) {
   do {                                                        \
     if (!(cond)) return ::vp::fail(VP_ERR_ARG, __VA_ARGS__);  \
   } while (0)
+
+// The A/B switches of the launch planner (launch_plan.h), looked up as each knob always was: VP_IGEMM16P and VP_IGEMM16P_M16 once per
+// process, the others through VP_GETENV (cached per process unless VP_ENV_DYNAMIC=1).  DESIGN.md section 13.
+inline PlanSwitches plan_switches() {
+  static const int p_mode = [] { const char* e = getenv("VP_IGEMM16P"); return e ? atoi(e) : 1; }();
+  static const bool p_m16 = [] { const char* e = getenv("VP_IGEMM16P_M16"); return !e || atoi(e) != 0; }();
+  auto on = [](const char* e) { return !(e && atoi(e) == 0); };
+  PlanSwitches sw;
+  sw.igemm16p_mode = p_mode;
+  sw.igemm16p_m16 = p_m16;
+  sw.igemm16_m16 = on(VP_GETENV("VP_IGEMM16_M16"));
+  sw.wgrad5 = on(VP_GETENV("VP_WGRAD5"));
+  sw.wgrad5f = on(VP_GETENV("VP_WGRAD5F"));
+  sw.wgrad_pair16 = on(VP_GETENV("VP_WGRAD_PAIR16"));
+  sw.f32_fast = on(VP_GETENV("VP_F32_FAST"));
+  if (const char* e = VP_GETENV("VP_WGRAD5_BLOCKS")) sw.wgrad5_blocks = atol(e);
+  return sw;
+}
 
 inline unsigned grid_for(size_t work_items, int block, unsigned cap = 256 * 8) {
   size_t g = (work_items + block - 1) / block;

@@ -335,16 +335,8 @@ size_t vp_conv5_wgrad_bf16x3_workspace_bytes(int B, int Hs, int Ws, int Cbig, in
 }
 
 size_t vp_conv_wgrad_bf16x3_workspace_bytes(int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride) {
-  ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
-  int ns = wgrad_nsplit(g);
-  if (wgrad_pair_applicable(g)) ns = wgrad_pair_nsplit(g, ns);   // tap pairs split twice as deep
-  size_t n = wgrad_slab_floats(g, ns);
-  if (const int bn = wgrad5_kind(g)) {                           // rows of taps: one slab set per CU-filling round
-    int kper = 0;
-    const size_t n5 = wgrad5_slab_floats(g, bn, wgrad5_nsplit(g, bn, &kper));
-    if (n5 > n) n = n5;
-  }
-  return n * sizeof(float);
+  const ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
+  return plan_wgrad(g, BF16X3, 0, SIZE_MAX, true, plan_switches()).query_floats * sizeof(float);
 }
 
 int vp_conv5_wgrad_bf16x3(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Cbig,
@@ -412,51 +404,44 @@ __global__ void __launch_bounds__(256) bn_stats_slab_final_kernel(const float* _
 extern "C" {
 
 size_t vp_conv5_stats_workspace_bytes(int family, int B, int Hs, int Ws, int Cbig, int Csmall, int stride) {
-  const StatPlan sp = stat_plan(family, B, Hs, Ws, Cbig, Csmall, stride);
-  return sp.ok ? (size_t)3 * sp.N * sp.tiles_m * sp.gz * sizeof(float) : 0;
+  return plan_stats(family, BF16X3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches()).stat_floats * sizeof(float);
 }
 
 }
 namespace vp {
-// the same finaliser for callers that do not see StatPlan (conv32.hip: the exact-f32 mode's statistics epilogue)
-int stats_slab_finish(const float* slab, int groups, int tiles_m, int bm, long M, long R, int N, float eps, float momentum, float* mean,
-                      float* rstd, float* rm, float* rv, hipStream_t stream) {
-  hipLaunchKernelGGL(bn_stats_slab_final_kernel, dim3(N), dim3(256), 0, stream, slab, groups, tiles_m, bm, M, R, N, eps, momentum, mean, rstd, rm, rv);
-  return check_launch("vp_conv5_*_stats_f32(final)");
+// the finaliser for every arithmetic: the slab geometry is the launch's plan
+int stats_finish(const ConvPlan& pl, const float* slab, float eps, float momentum, float* mean, float* rstd, float* rm, float* rv, hipStream_t stream,
+                 const char* what) {
+  hipLaunchKernelGGL(bn_stats_slab_final_kernel, dim3((unsigned)pl.N), dim3(256), 0, stream, slab, pl.stat_tiles_m * pl.gz, pl.stat_tiles_m, pl.bm,
+                     pl.M, pl.stat_R, (int)pl.N, eps, momentum, mean, rstd, rm, rv);
+  return check_launch(what);
 }
 }  // namespace vp
-int vp16_stats_finish(const StatPlan& sp, const float* slab, float eps, float momentum, float* mean, float* rstd, float* rm, float* rv,
-                        vp_stream stream) {
-  hipLaunchKernelGGL(bn_stats_slab_final_kernel, dim3(sp.N), dim3(256), 0, (hipStream_t)stream, slab, sp.tiles_m * sp.gz, sp.tiles_m, sp.bm,
-                     sp.M, sp.R, sp.N, eps, momentum, mean, rstd, rm, rv);
-  return check_launch("vp_conv5_*_stats_bf16x3(final)");
-}
 extern "C" {
 
 int vp_conv5_gather_stats_bf16x3(const void* big_split, const void* w_p0_split, float* small_out, int B, int Hs, int Ws, int Cbig,
                                  int Csmall, int stride, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                                  float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(big_split && w_p0_split && small_out && mean && rstd && ws, "vp_conv5_gather_stats_bf16x3: null pointer");
-  const StatPlan sp = stat_plan(0, B, Hs, Ws, Cbig, Csmall, stride);
-  VP_REQUIRE(sp.ok, "vp_conv5_gather_stats_bf16x3: this shape cannot emit statistics (vp_conv5_stats_workspace_bytes() == 0)");
-  if (ws_bytes < (size_t)3 * sp.N * sp.tiles_m * sp.gz * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_gather_stats_bf16x3: workspace too small");
-  int rc = gather16_t<ProbF16>(big_split, w_p0_split, nullptr, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride,
-                               VP_ACT_NONE, true, stream, (float*)ws);
+  const ConvPlan pl = plan_stats(0, BF16X3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
+  VP_REQUIRE(pl.stat_ok, "vp_conv5_gather_stats_bf16x3: this shape cannot emit statistics (vp_conv5_stats_workspace_bytes() == 0)");
+  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_gather_stats_bf16x3: workspace too small");
+  int rc = gather16_t<ProbF16>(pl, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), big_split, w_p0_split, nullptr, small_out, VP_ACT_NONE, stream,
+                               (float*)ws);
   if (rc) return rc;
-  return vp16_stats_finish(sp, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, stream);
+  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
 }
 
 int vp_conv5_scatter_stats_bf16x3(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
                                   int Cbig, int stride, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                                   float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(small_split && w_p1_split && big_out && mean && rstd && ws, "vp_conv5_scatter_stats_bf16x3: null pointer");
-  const StatPlan sp = stat_plan(1, B, Hs, Ws, Cbig, Csmall, stride);
-  VP_REQUIRE(sp.ok, "vp_conv5_scatter_stats_bf16x3: this shape cannot emit statistics (vp_conv5_stats_workspace_bytes() == 0)");
-  if (ws_bytes < (size_t)3 * sp.N * sp.tiles_m * sp.gz * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_scatter_stats_bf16x3: workspace too small");
-  int rc = scatter16_t<ProbT16>(small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride, true, stream,
-                                (float*)ws);
+  const ConvPlan pl = plan_stats(1, BF16X3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
+  VP_REQUIRE(pl.stat_ok, "vp_conv5_scatter_stats_bf16x3: this shape cannot emit statistics (vp_conv5_stats_workspace_bytes() == 0)");
+  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_scatter_stats_bf16x3: workspace too small");
+  int rc = scatter16_t<ProbT16>(pl, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), small_split, w_p1_split, big_out, stream, (float*)ws);
   if (rc) return rc;
-  return vp16_stats_finish(sp, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, stream);
+  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
 }
 
 

@@ -52,8 +52,7 @@ int vp_conv_wgrad_f16x2(const void* big_split, const void* small_split, float* d
 
 // the same on fp16-pair planes (forward layers: out_scale is 1)
 size_t vp_conv5_stats_f16_workspace_bytes(int family, int B, int Hs, int Ws, int Cbig, int Csmall, int stride) {
-  const StatPlan sp = stat_plan(family, B, Hs, Ws, Cbig, Csmall, stride, true);
-  return sp.ok ? (size_t)3 * sp.N * sp.tiles_m * sp.gz * sizeof(float) : 0;
+  return plan_stats(family, F16_2, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches()).stat_floats * sizeof(float);
 }
 
 int vp_conv5_gather_stats_f16(const void* big_split, const void* w_p0_split, float* small_out, int B, int Hs, int Ws, int Cbig,
@@ -61,15 +60,14 @@ int vp_conv5_gather_stats_f16(const void* big_split, const void* w_p0_split, flo
                               float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(products == 2 || products == 3, "vp_conv5_gather_stats_f16: products must be 2 or 3");
   VP_REQUIRE(big_split && w_p0_split && small_out && mean && rstd && ws, "vp_conv5_gather_stats_f16: null pointer");
-  const StatPlan sp = stat_plan(0, B, Hs, Ws, Cbig, Csmall, stride, true);
-  VP_REQUIRE(sp.ok, "vp_conv5_gather_stats_f16: this shape cannot emit statistics (vp_conv5_stats_f16_workspace_bytes() == 0)");
-  if (ws_bytes < (size_t)3 * sp.N * sp.tiles_m * sp.gz * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_gather_stats_f16: workspace too small");
-  int rc = products == 2 ? gather16_t<ProbF16X>(big_split, w_p0_split, nullptr, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5,
-                                                stride, VP_ACT_NONE, true, stream, (float*)ws)
-                         : gather16_t<ProbF16H>(big_split, w_p0_split, nullptr, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5,
-                                                stride, VP_ACT_NONE, true, stream, (float*)ws);
+  const ConvPlan pl = plan_stats(0, products == 2 ? F16_2 : F16_3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
+  VP_REQUIRE(pl.stat_ok, "vp_conv5_gather_stats_f16: this shape cannot emit statistics (vp_conv5_stats_f16_workspace_bytes() == 0)");
+  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_gather_stats_f16: workspace too small");
+  const ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5);
+  int rc = products == 2 ? gather16_t<ProbF16X>(pl, g, big_split, w_p0_split, nullptr, small_out, VP_ACT_NONE, stream, (float*)ws)
+                         : gather16_t<ProbF16H>(pl, g, big_split, w_p0_split, nullptr, small_out, VP_ACT_NONE, stream, (float*)ws);
   if (rc) return rc;
-  return vp16_stats_finish(sp, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, stream);
+  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
 }
 
 int vp_conv5_scatter_stats_f16(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
@@ -77,15 +75,14 @@ int vp_conv5_scatter_stats_f16(const void* small_split, const void* w_p1_split, 
                                float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(products == 2 || products == 3, "vp_conv5_scatter_stats_f16: products must be 2 or 3");
   VP_REQUIRE(small_split && w_p1_split && big_out && mean && rstd && ws, "vp_conv5_scatter_stats_f16: null pointer");
-  const StatPlan sp = stat_plan(1, B, Hs, Ws, Cbig, Csmall, stride, true);
-  VP_REQUIRE(sp.ok, "vp_conv5_scatter_stats_f16: this shape cannot emit statistics (vp_conv5_stats_f16_workspace_bytes() == 0)");
-  if (ws_bytes < (size_t)3 * sp.N * sp.tiles_m * sp.gz * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_scatter_stats_f16: workspace too small");
-  int rc = products == 2 ? scatter16_t<ProbT16X>(small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride,
-                                                 true, stream, (float*)ws)
-                         : scatter16_t<ProbT16H>(small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride,
-                                                 true, stream, (float*)ws);
+  const ConvPlan pl = plan_stats(1, products == 2 ? F16_2 : F16_3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
+  VP_REQUIRE(pl.stat_ok, "vp_conv5_scatter_stats_f16: this shape cannot emit statistics (vp_conv5_stats_f16_workspace_bytes() == 0)");
+  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_scatter_stats_f16: workspace too small");
+  const ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5);
+  int rc = products == 2 ? scatter16_t<ProbT16X>(pl, g, small_split, w_p1_split, big_out, stream, (float*)ws)
+                         : scatter16_t<ProbT16H>(pl, g, small_split, w_p1_split, big_out, stream, (float*)ws);
   if (rc) return rc;
-  return vp16_stats_finish(sp, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, stream);
+  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
 }
 
 }

@@ -309,15 +309,7 @@ static int halo_launch(HaloArgs a, hipStream_t s, const char* what) {
   return check_launch(what);
 }
 
-// ---- host dispatch ---------------------------------------------------------------------------------
-int halo_gather_kind(int B, int Hs, int Ws, int Cbig, int Csmall, int stride) {
-  if (Ws % 16 != 0 || B <= 0) return 0;
-  if (Cbig % 32 == 0 && Cbig <= 128 && stride == 1 && Csmall <= 32 && Hs % 16 == 0) return 1;
-  if (Cbig == 32 && stride == 2 && Csmall >= 64 && Hs % 8 == 0) return 2;
-  if (Cbig == 8 && stride == 2 && Hs % 8 == 0) return 3;
-  return 0;
-}
-
+// ---- host dispatch (which shapes: halo_gather_kind / halo_scatter_kind, launch_plan.h) -------------
 int halo_gather_launch(int kind, const void* big_split, const void* w_p0_split, const float* bias, float* out, int B, int Hs, int Ws,
                        int Cbig, int Csmall, int stride, int act, hipStream_t s) {
   HaloArgs a{};
@@ -334,11 +326,6 @@ int halo_gather_launch(int kind, const void* big_split, const void* w_p0_split, 
     return halo_launch<32, 2, 2, 1, 2, 2, false>(a, s, "halo_gather<32,s2,64>");
   }
   return halo_launch<8, 2, 2, 1, 2, 2, false>(a, s, "halo_gather<8,s2>");
-}
-
-int halo_scatter_kind(int B, int Hs, int Ws, int Csmall, int Cbig, int stride) {
-  if (stride == 1 && Csmall == 8 && Ws % 16 == 0 && Hs % 16 == 0 && B > 0) return 1;
-  return 0;
 }
 
 int halo_scatter_launch(int kind, const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,

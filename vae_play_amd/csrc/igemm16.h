@@ -23,7 +23,7 @@
 #include <string.h>
 #include <hip/hip_runtime.h>
 #include <cstdlib>
-#include "problems.h"
+#include "launch_plan.h"
 #if defined(__HIPCC__)
 #include "split.h"
 #endif
@@ -1048,88 +1048,62 @@ __global__ void __launch_bounds__(256, (M16 && BM * BN >= 128 * 128) ? 2 : 1) ig
 #ifndef VP_IGEMM16_M16_ON
 #define VP_IGEMM16_M16_ON 0      // translation units that dispatch the 16x16x32 form of igemm16_kernel define it to 1 (conv16.hip)
 #endif
-struct Tile16 { int bm, bn; };   // wave grid: 2 x 2, or 4 x 1 for the 32-column tiles
 
-inline Tile16 choose_tile16(long M, long N, int gz, bool /*pixel_major*/ = false, int ctile = 0) {
-  auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * (long)gz; };
-  const long MINB = 384;      // (per-shape tile searches on the VAE and VAE-GAN steps found nothing beyond noise: profiles/r02_notes.md section 7)
-  // a 32-column operand (the 32-channel end of the last decoder block): 64-column tiles would idle half the MFMAs.
-  // Unless k runs over 64-channel chunks (ctile = the gathered / scattered side's channel count) and the launch is large: the
-  // 32-column tiles exist with 32-deep K-tiles only, and the 64x64 tile on 64-deep FAST K-tiles is 1.4-2.3x faster there even
-  // with half of its MFMA columns idle (profiles/r02_g_narrow_n_microbench.log: gather 5x5 s2 64 -> 32 channels 238 -> 106 us, the VAE-GAN
-  // discriminator's 64 -> 32 input gradient 252 -> 175 us; 32- and 40-channel chunks keep the narrow tiles: 134 vs 173 us).
-  const bool deep = ctile > 0 && ctile % 64 == 0 && (gz == 1 || M * gz >= (1L << 19));
-  if (N <= 32 && M >= 128 && !deep) return (M >= 256 && blocks(256, 32) >= MINB) ? Tile16{256, 32} : Tile16{128, 32};
-  if (M >= 128 && N >= 128 && blocks(128, 128) >= MINB) return {128, 128};
-  if (M >= 128 && N >= 64 && blocks(128, 64) >= MINB) return {128, 64};
-  return {64, 64};
-}
+// ---- the one dispatch from a planned (tile, K-tile depth, FAST, m16) to the kernel instantiation (launch_plan.h decides) ---------
+// A caller names the (depth, FAST) forms and the tiles that its problem type may instantiate, which keeps compile time and the code
+// object down; a plan outside that set launches nothing and returns false (an error for the caller, never a silent fall-back).
+enum : unsigned { K64F = 1, K32F = 2, K64S = 4, K32S = 8 };      // K-tile depth 64 | 32, FAST | with channel tails
+enum : unsigned { T128x128 = 1, T128x64 = 2, T64x64 = 4, T256x32 = 8, T128x32 = 16, T64x128 = 32 };
+constexpr unsigned T_SQUARE = T128x128 | T128x64 | T64x64, T_N32 = T256x32 | T128x32;      // (32-column tiles: 32-deep K-tiles only)
 
-// K-tile depth: 64 for the gather/scatter families (half the barriers per MFMA), 32 for the weight
-// gradient (its [pixel][channel] LDS images at depth 64 leave one workgroup per CU).  Measured on
-// MI355X, profiles/.
-inline int igemm16_bk(bool km, bool x2 = false) {
-  // the two-product fp16 mode stages three planes instead of four: the weight gradient's 64-deep K-tile then leaves two
-  // workgroups per CU (61 KB each) and halves its barriers (measured -20 us per step, f16x2)
-  return km ? (x2 ? 64 : 32) : 64;
-}
-
-template <class P, int BKT, bool FAST>
-inline void launch_igemm16_bk(const P& p, long M, long N, int gz, hipStream_t stream, int ctile = 0, bool m16 = false) {
-  Tile16 t = choose_tile16(M, N, gz, P::A_KM, ctile);
-  dim3 block(256);
-  auto grid = [&](int bm, int bn) { return dim3((unsigned)((M + bm - 1) / bm), (unsigned)((N + bn - 1) / bn), (unsigned)gz); };
+template <class P, unsigned TILES, int BKT, bool FAST>
+inline bool launch_form16(const P& p, int bm, int bn, bool m16, dim3 grid, hipStream_t stream) {
+  const dim3 block(256);
   if constexpr (VP_IGEMM16_M16_ON && !P::A_KM && !P::B_KM && P::MODE == 0 && P::IS_K5 && BKT == 64 && FAST) {
-    if (m16 && t.bm == 128 && (t.bn == 128 || t.bn == 64)) {      // the 16x16x32 form of the same tiles (the host decides where: igemm16_m16_rule)
-      if (t.bn == 128) hipLaunchKernelGGL((igemm16_kernel<P, 128, 128, 2, 2, BKT, FAST, true>), grid(128, 128), block, 0, stream, p);
-      else hipLaunchKernelGGL((igemm16_kernel<P, 128, 64, 2, 2, BKT, FAST, true>), grid(128, 64), block, 0, stream, p);
-      return;
-    }
+    if (m16 && bm == 128 && bn == 128) { hipLaunchKernelGGL((igemm16_kernel<P, 128, 128, 2, 2, BKT, FAST, true>), grid, block, 0, stream, p); return true; }
+    if (m16 && bm == 128 && bn == 64) { hipLaunchKernelGGL((igemm16_kernel<P, 128, 64, 2, 2, BKT, FAST, true>), grid, block, 0, stream, p); return true; }
   }
-  if (t.bm == 128 && t.bn == 128) {
-    hipLaunchKernelGGL((igemm16_kernel<P, 128, 128, 2, 2, BKT, FAST>), grid(128, 128), block, 0, stream, p);
-  } else if (t.bm == 128 && t.bn == 64) {
-    hipLaunchKernelGGL((igemm16_kernel<P, 128, 64, 2, 2, BKT, FAST>), grid(128, 64), block, 0, stream, p);
-  } else if (t.bn == 32) {
-    // 32-column tiles run 32-deep K-tiles (LDS budget: 2-3 workgroups per CU)
-    if constexpr (BKT == 32) {
-      if (t.bm == 256) hipLaunchKernelGGL((igemm16_kernel<P, 256, 32, 4, 1, 32, FAST>), grid(256, 32), block, 0, stream, p);
-      else hipLaunchKernelGGL((igemm16_kernel<P, 128, 32, 4, 1, 32, FAST>), grid(128, 32), block, 0, stream, p);
+#define VP_TILE16(T, BM, BN, WM, WN)                                                                          \
+  if constexpr ((TILES & (T)) != 0 && (BN != 32 || BKT == 32))                                                \
+    if (bm == BM && bn == BN) {                                                                               \
+      hipLaunchKernelGGL((igemm16_kernel<P, BM, BN, WM, WN, BKT, FAST>), grid, block, 0, stream, p);          \
+      return true;                                                                                            \
     }
-  } else {
-    hipLaunchKernelGGL((igemm16_kernel<P, 64, 64, 2, 2, BKT, FAST>), grid(64, 64), block, 0, stream, p);
-  }
+  VP_TILE16(T128x128, 128, 128, 2, 2)
+  VP_TILE16(T128x64, 128, 64, 2, 2)
+  VP_TILE16(T64x64, 64, 64, 2, 2)
+  VP_TILE16(T256x32, 256, 32, 4, 1)
+  VP_TILE16(T128x32, 128, 32, 4, 1)
+  VP_TILE16(T64x128, 64, 128, 2, 2)
+#undef VP_TILE16
+  return false;
 }
 
-// ctile = the channel count that k is decomposed by (0 for the pixel-major wgrad family): FAST kernels
-// are used when it is a multiple of the K-tile depth.
+template <class P, unsigned FORMS, unsigned TILES>
+inline bool launch_tiles16(const P& p, int bm, int bn, int bk, bool fast, bool m16, long M, long N, int gz, hipStream_t stream) {
+  if (bm <= 0 || bn <= 0) return false;
+  const dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)((N + bn - 1) / bn), (unsigned)gz);
+  if constexpr ((FORMS & K64F) != 0) if (bk == 64 && fast) return launch_form16<P, TILES, 64, true>(p, bm, bn, m16, grid, stream);
+  if constexpr ((FORMS & K32F) != 0) if (bk == 32 && fast) return launch_form16<P, TILES, 32, true>(p, bm, bn, false, grid, stream);
+  if constexpr ((FORMS & K64S) != 0) if (bk == 64 && !fast) return launch_form16<P, TILES, 64, false>(p, bm, bn, false, grid, stream);
+  if constexpr ((FORMS & K32S) != 0) if (bk == 32 && !fast) return launch_form16<P, TILES, 32, false>(p, bm, bn, false, grid, stream);
+  return false;
+}
+
+// the forms of the generic dispatch: every one, but no 64-deep FAST K-tile for the pixel-major weight gradient outside the two-product
+// fp16 mode (wgrad_form, launch_plan.h)
+template <class P> constexpr unsigned forms16() { return (!P::A_KM || P::X2) ? (K64F | K32F | K64S | K32S) : (K32F | K64S | K32S); }
+
+// Plans and launches in one call, for callers without a ConvPlan: the pixel-major weight gradient (ctile = 0) and tools/kbench.
+// ctile = the channel count that k is decomposed by.
 template <class P>
 inline void launch_igemm16(const P& p, long M, long N, int gz, hipStream_t stream, int ctile = 0, bool m16 = false) {
-  const int bk = igemm16_bk(P::A_KM, P::X2);
-  if constexpr (P::A_KM) {
-    // pixel-major (wgrad) family: FAST when the chosen tile lies fully inside M x N (no channel tails)
-    Tile16 t = choose_tile16(M, N, gz, true);
-    const bool fast = (M % t.bm == 0) && (N % t.bn == 0);
-    if (bk == 32) {
-      if (fast) launch_igemm16_bk<P, 32, true>(p, M, N, gz, stream);
-      else launch_igemm16_bk<P, 32, false>(p, M, N, gz, stream);
-    } else if (t.bn == 32) {
-      if (fast) launch_igemm16_bk<P, 32, true>(p, M, N, gz, stream);
-      else launch_igemm16_bk<P, 32, false>(p, M, N, gz, stream);
-    } else {
-      if constexpr (P::X2) {
-        if (fast) { launch_igemm16_bk<P, 64, true>(p, M, N, gz, stream); return; }
-      }
-      launch_igemm16_bk<P, 64, false>(p, M, N, gz, stream);
-    }
-  } else {
-    const Tile16 t0 = choose_tile16(M, N, gz, false, ctile);
-    const bool narrow = t0.bn == 32;   // tiles that exist with 32-deep K-tiles only
-    if (ctile > 0 && ctile % 64 == 0 && bk == 64 && !narrow) launch_igemm16_bk<P, 64, true>(p, M, N, gz, stream, ctile, m16);
-    else if (ctile > 0 && ctile % 32 == 0) launch_igemm16_bk<P, 32, true>(p, M, N, gz, stream, ctile);   // 32-channel chunks
-    else if (bk == 32 || narrow) launch_igemm16_bk<P, 32, false>(p, M, N, gz, stream, ctile);
-    else launch_igemm16_bk<P, 64, false>(p, M, N, gz, stream, ctile);
-  }
+  const Tile16 t = choose_tile16(M, N, gz, P::A_KM ? 0 : ctile);
+  int bk;
+  bool fast;
+  if constexpr (P::A_KM) wgrad_form(M, N, t, P::X2, bk, fast);
+  else staged_form(ctile, t.bn, bk, fast);
+  launch_tiles16<P, forms16<P>(), T_SQUARE | T_N32>(p, t.bm, t.bn, bk, fast, m16, M, N, gz, stream);
 }
 #endif  // __HIPCC__
 

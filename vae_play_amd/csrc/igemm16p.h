@@ -435,36 +435,13 @@ __global__ void __launch_bounds__(WM * WN * 64, MINW) igemm16p_kernel(const P p)
 #endif
 }
 
-// tile configurations of the pipelined kernel
-enum PCfg : int {
-  PCFG_NONE = 0,
-  PCFG_128x128_S3,     // 4 waves 2x2, 96 KB: one workgroup per CU
-  PCFG_128x128_S2,     // 4 waves 2x2, 64 KB: two workgroups per CU
-  PCFG_256x128_S3,     // 8 waves 4x2, 144 KB
-  PCFG_256x64_S3,      // 4 waves 4x1, 120 KB
-  PCFG_256x64_S2,      // 4 waves 4x1, 80 KB: two per CU
-  PCFG_256x256_S2,     // 8 waves 2x4 (wave tile 128x64), 128 KB
-  PCFG_128x64_S3,      // 4 waves 2x2 (wave tile 64x32), 72 KB: two per CU
-  PCFG_COUNT
-};
-
-inline void pcfg_tile(int cfg, int& bm, int& bn) {
-  switch (cfg) {
-    case PCFG_128x128_S3: case PCFG_128x128_S2: bm = 128; bn = 128; break;
-    case PCFG_256x128_S3: bm = 256; bn = 128; break;
-    case PCFG_256x64_S3: case PCFG_256x64_S2: bm = 256; bn = 64; break;
-    case PCFG_256x256_S2: bm = 256; bn = 256; break;
-    case PCFG_128x64_S3: bm = 128; bn = 64; break;
-    default: bm = bn = 0;
-  }
-}
-
+// (tile configurations: enum PCfg and pcfg_tile, launch_plan.h)
 template <class P, int KORD, bool BUF, bool M16>
 inline void launch_igemm16p_k(const P& p, int cfg, long M, long N, int gz, hipStream_t stream) {
   int bm, bn;
   pcfg_tile(cfg, bm, bn);
   const dim3 grid((unsigned)((M + bm - 1) / bm), (unsigned)((N + bn - 1) / bn), (unsigned)gz);
-  // The library (VP_PCFG_LIBRARY, set by conv16.hip) instantiates only what plan16 dispatches: buffer DMA, the 256x256 and 128x64
+  // The library (VP_PCFG_LIBRARY, set by conv16.hip) instantiates only what plan_conv (launch_plan.h) dispatches: buffer DMA, the 256x256 and 128x64
   // tiles on the 32x32x16 MFMA and the 256x128 tile on the 16x16x32 form; tools/kbench compiles every configuration.
 #if defined(VP_PCFG_LIBRARY)
 #define VP_PCFG_ON(plain, q) (BUF && (M16 ? (q) : (plain)))

@@ -602,45 +602,11 @@ __global__ void __launch_bounds__(512) wgrad5f_kernel(const ProbW5F p) {
 #endif  // __HIPCC__
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// Shapes the row-of-taps kernel takes: plain 5x5 stride-2 layers (Hb = 2*Hs), 128 | Cs, Cb a multiple of 128 or exactly 64,
-// K-tiles of 32 pixels that are whole image rows (Ws in {8, 16}) or row segments (32 | Ws), 32-bit element offsets.
-inline int wgrad5_bn(const ConvGeom& g) {
-  if (g.ks != 5 || g.stride != 2 || g.Hb != 2 * g.Hs || g.Wb != 2 * g.Ws) return 0;
-  if (g.Cs % 128 != 0) return 0;
-  const int bn = g.Cb % 128 == 0 ? 128 : (g.Cb == 64 ? 64 : 0);
-  if (!bn) return 0;
-  const bool wok = g.Ws % 32 == 0 || g.Ws == 16 || g.Ws == 8;
-  if (!wok || ((long)g.Hs * g.Ws) % 32 != 0) return 0;
-  if ((size_t)g.B * g.Hb * g.Wb * g.Cb >= ((size_t)1 << 31) || (size_t)g.B * g.Hs * g.Ws * g.Cs >= ((size_t)1 << 31)) return 0;
-  return bn;
-}
-
-// pixel ranges: one workgroup per CU (the kernel holds 160 accumulators per lane at two waves per SIMD), i.e. ~256 work items
-// `items` = work items (= CUs, the kernel owns one per work item) the launch may take; <= 0: the whole chip.  A caller that runs the
-// weight gradient beside other kernels leaves part of the chip to them: on the side stream of the fused step ~5/8 of the chip is
-// the measured optimum (step 3.588 ms with the one-tap kernels; rows of taps with 256 work items 3.52, 176: 3.479, 160: 3.455,
-// 144: 3.471, 128: 3.484, 96: 3.67 -- profiles/r03_notes.md): the main stream's kernels keep the rest instead of queueing behind
-// one-workgroup-per-CU launches, and the slabs shrink with the count.
-// A budget above the chip's WGRAD5_MAX_ITEMS CUs (MI355X: 256) means nothing more and is clamped to it: the workspace queries size
-// the slabs for items = 0, i.e. WGRAD5_MAX_ITEMS, so a larger count would split K deeper than the queried workspace holds.
-constexpr int WGRAD5_MAX_ITEMS = 256;
+// Which shapes the kernel takes, its pixel-range split and its slab size: wgrad5_bn, wgrad5_split, wgrad5_slab_floats (launch_plan.h).
+// For tools/kbench, which has no plan: the split with VP_WGRAD5_BLOCKS looked up as the library does.
 inline int wgrad5_nsplit(const ConvGeom& g, int bn, int* k_per_split, int items = 0) {
-  const long K = (long)g.B * g.Hs * g.Ws;
-  const long inner = (long)(g.Cs / 128) * (g.Cb / bn) * 5;
-  long target = items > 0 && items < WGRAD5_MAX_ITEMS ? items : WGRAD5_MAX_ITEMS;
-  if (const char* e = VP_GETENV("VP_WGRAD5_BLOCKS")) target = atol(e);       // A/B knob: overrides the caller's count
-  long ns = target / inner;
-  if (ns < 1) ns = 1;
-  const long maxs = K / 128 > 0 ? K / 128 : 1;                               // at least four K-tiles per split
-  if (ns > maxs) ns = maxs;
-  long per = ((K + ns - 1) / ns + 31) / 32 * 32;
-  ns = (K + per - 1) / per;                                                  // no empty split
-  *k_per_split = (int)per;
-  return (int)ns;
-}
-
-inline size_t wgrad5_slab_floats(const ConvGeom& g, int bn, int ns) {
-  return (size_t)ns * (bn == 64 ? 2 : 1) * 25 * g.Cs * g.Cb;
+  const char* e = VP_GETENV("VP_WGRAD5_BLOCKS");
+  return wgrad5_split(g, bn, items, e ? atol(e) : WGRAD5_BLOCKS_UNSET, k_per_split);
 }
 
 #if defined(__HIPCC__)

@@ -25,11 +25,9 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, ops, parallel
+from . import _lib, ops, parallel, sections
 from .networks import VAE
-from .plan import FWD_PRODUCTS, PlanBuilder, _Plan, _ptr, grad_of, plan_device, side_ctx, sync_counters_on_state_dict
-
-_ACT_NONE, _ACT_SIGMOID = ops.ACT_NONE, ops.ACT_SIGMOID
+from .plan import PlanBuilder, _Plan, _ptr, plan_device, side_ctx, sync_counters_on_state_dict
 
 
 class FusedVAEStep:
@@ -104,15 +102,8 @@ class FusedVAEStep:
                         wgrad_cus=(int(env("VP_WGRAD_MAIN_CUS", "0")), int(env("VP_WGRAD_SIDE_CUS", "160"))),
                         grad_scale16=self.grad_scale16, sat=self._f16_sat, fuse_stats=env("VP_FUSE_BN_STATS", "1") != "0")
         lib = b.lib
-        x2 = b.x2                                      # fp16-pair planes + the *_f16x2 launches (same plan structure)
-        FMT = 1 if x2 else 0                           # VP_SPLIT_F16 | VP_SPLIT_BF16
-        GS = b.GS
-        a16 = self.precision if x3 else "f32"          # arithmetic of the 5x5 layers whose channel counts are multiples of 8
 
-        def use16(cin, cout):
-            return x3 and cin % 8 == 0 and cout % 8 == 0
-
-        # ---------------- forward ----------------
+        # ---------------- forward: stem / encoder blocks -> head -> trunk -> loss ----------------
         self.x_nchw = b.buf("x_nchw", B, C, S, S)
         self.eps = b.buf("eps", B, Z)
         x_nhwc = b.buf("x_nhwc", B * S * S * C)
@@ -120,144 +111,22 @@ class FusedVAEStep:
             fwd.add("vp_nchw_to_nhwc_f32", P(self.x_nchw), P(x_nhwc), B, C, S, S)
         else:
             x_nhwc = self.x_nchw  # identical memory order for one channel
-
-        enc_ch = [C] + [blk.conv.weight.shape[0] for blk in enc.conv]
-        sp = [S // (2 ** i) for i in range(L + 1)]
-        enc16 = [use16(enc_ch[i], enc_ch[i + 1]) for i in range(L)]
-        enc0_cols = x3 and C in (1, 3) and enc_ch[1] % 8 == 0
-        # exact f32: the same im2col as plain fp32, both 1x1 layers on the fp32-MFMA kernels (the 3-channel implicit GEMM and the VALU
-        # weight gradient took 48 + 67 us at the benchmark shard, the two 1x1 layers 36 + 40 + 20 us of im2col / re-order: 7.63 -> 7.60 ms)
-        enc0_cols32 = (not x3) and C in (1, 3) and enc_ch[1] % 16 == 0
-        enc_in = [x_nhwc]        # fp32 inputs (None when only the split copy exists)
-        enc_in_s = [None]        # split inputs
-        enc_rec = []
-        for i, blk in enumerate(enc.conv):
+        blocks = sections.gather_stack(b, "enc", enc.conv, B, S, x_nhwc, None, image=self.x_nchw)
+        for i, blk in enumerate(blocks):
             if i == 1 and b.k_pack is not None:
                 fwd.wait_side(b.k_pack)
-            Cin, Cout, Hs = enc_ch[i], enc_ch[i + 1], sp[i + 1]
-            n_out = B * Hs * Hs * Cout
-            c = b.buf(f"enc{i}.c", n_out)
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            geom = (B, Hs, Hs, Cin, Cout, 2)
-            conv = None
-            if i == 0 and enc0_cols:
-                # first conv (1 or 3 image channels): im2col written once as split planes, then a 1x1 layer on the MFMA kernels
-                KC = lib.vp_im2col5s2_cols(Cin)
-                xcol = b.sbuf("enc0.xcol", B * Hs * Hs * KC)
-                w0s = b.sbuf("enc0.w0s", Cout * KC)
-                if x2:
-                    fwd.add("vp_im2col5s2_split_fmt_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1, FMT)
-                    fwd.add("vp_pack_w_im2col5_split_fmt", P(blk.conv.weight), P(w0s), Cout, Cin, FMT)
-                    fwd.add("vp_conv_gather_f16", P(xcol), P(w0s), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE, FWD_PRODUCTS, 1.0,
-                            flops=fl, tag="enc0.fwd")
-                else:
-                    fwd.add("vp_im2col5s2_split_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1)
-                    fwd.add("vp_pack_w_im2col5_split", P(blk.conv.weight), P(w0s), Cout, Cin)
-                    fwd.add("vp_conv_gather_bf16x3", P(xcol), P(w0s), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE,
-                            flops=fl, tag="enc0.fwd")
-                p1, enc0 = None, (xcol, KC)
-            elif i == 0 and enc0_cols32:
-                KC = lib.vp_im2col5s2_cols(Cin)
-                xcol = b.buf("enc0.xcol32", B * Hs * Hs * KC)
-                w0 = b.buf("enc0.w0", Cout * KC)
-                fwd.add("vp_im2col5s2_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1)
-                fwd.add("vp_pack_w_im2col5_f32", P(blk.conv.weight), P(w0), Cout, Cin)
-                fwd.add("vp_conv_gather_f32", P(xcol), P(w0), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE, flops=fl, tag="enc0.fwd")
-                p1, enc0 = None, (xcol, KC)
-            elif enc16[i]:
-                p0 = b.sbuf(f"enc{i}.p0s", Cout * 25 * Cin)
-                p1 = b.sbuf(f"enc{i}.p1s", Cin * 25 * Cout)
-                b.pack(blk.conv.weight, p0, p1, Cout, Cin, True, first=(i == 0))
-                conv = (0, a16, enc_in_s[-1], p0, geom, fl)
-            else:
-                p0 = b.buf(f"enc{i}.p0", Cout * 25 * Cin)
-                p1 = b.buf(f"enc{i}.p1", Cin * 25 * Cout) if i > 0 else None
-                b.pack(blk.conv.weight, p0, p1, Cout, Cin, False, first=(i == 0))
-                conv = (0, "f32", enc_in[-1], p0, geom, fl)
-            # the activation feeds the next conv (+ its wgrad) or, for the last block, the flatten
-            nxt16 = i + 1 < L and enc16[i + 1]
-            a = None if nxt16 else b.buf(f"enc{i}.a", n_out)
-            a_s = b.sbuf(f"enc{i}.as", n_out) if nxt16 else None
-            saved = b.bn_fwd(fwd, f"enc{i}", c, B * Hs * Hs, Cout, blk.bn, a, a_s, conv=conv)
-            enc_rec.append((blk, Cin, Cout, Hs, p1, c, saved))
-            enc_in.append(a)
-            enc_in_s.append(a_s)
+            blk.fwd(fwd)
         if L == 1 and b.k_pack is not None:
             fwd.wait_side(b.k_pack)
-        size = enc_ch[-1]
-        F0 = 64 * size
-        flat = b.buf("enc.flat", B * F0)
-        fwd.add("vp_nhwc_to_nchw_f32", P(enc_in[-1]), P(flat), B, size, 8, 8)
-        fc_lin, fc_bn = enc.fc[0], enc.fc[1]
-        h = b.buf("enc.h", B * 1024)
-        hb = b.buf("enc.hb", B * 1024)
-        b.lin_fwd(fwd, flat, fc_lin.weight, None, h, B, 1024, F0)
-        h_saved = b.bn_fwd(fwd, "enc.fc", h, B, 1024, fc_bn, hb)
-        self.mu, self.logvar = b.buf("mu", B, Z), b.buf("logvar", B, Z)
-        for lin, out in ((enc.l_mu, self.mu), (enc.l_var, self.logvar)):
-            b.lin_fwd(fwd, hb, lin.weight, lin.bias, out, B, Z, 1024)
-        self.z, self.kl = b.buf("z", B, Z), b.buf("kl", B)
-        fwd.add("vp_latent_fwd_f32", P(self.mu), P(self.logvar), P(self.eps), P(self.z), P(self.kl), B, Z)
-
-        dfc_lin, dfc_bn = dec.fc[0], dec.fc[1]
-        dsize = dec._c0
-        F1 = 64 * dsize
-        d = b.buf("dec.d", B * F1)
-        db = b.buf("dec.db", B * F1)
-        b.lin_fwd(fwd, self.z, dfc_lin.weight, None, d, B, F1, Z)
-        d_saved = b.bn_fwd(fwd, "dec.fc", d, B, F1, dfc_bn, db)
-        dec_ch = [dsize] + [blk.conv.weight.shape[1] for blk in list(dec.conv)[:L]]
-        dec16 = [use16(dec_ch[i], dec_ch[i + 1]) for i in range(L)]
-        dn = None if dec16[0] else b.buf("dec.in", B * F1)
-        dn_s = b.sbuf("dec.in_s", B * F1) if dec16[0] else None
-        if x2:
-            fwd.add("vp_nchw_to_nhwc_split_fmt_f32", P(db), P(dn), P(dn_s), B, dsize, 8, 8, FMT)
-        else:
-            fwd.add("vp_nchw_to_nhwc_split_f32", P(db), P(dn), P(dn_s), B, dsize, 8, 8)
-
-        dec_in = [dn]
-        dec_in_s = [dn_s]
-        dec_rec = []
-        for i in range(L):
-            blk = dec.conv[i]
-            Cin, Cout, Hs = dec_ch[i], dec_ch[i + 1], 8 * (2 ** i)
-            n_out = B * 4 * Hs * Hs * Cout
-            tbuf = b.buf(f"dec{i}.t", n_out)
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            geom = (B, Hs, Hs, Cin, Cout, 2)
-            if dec16[i]:
-                p1 = b.sbuf(f"dec{i}.p1s", Cout * 25 * Cin)   # T family: [Cbig=Cout][25][Csmall=Cin]
-                p0 = b.sbuf(f"dec{i}.p0s", Cin * 25 * Cout)   # F family (dgrad): [Csmall=Cin][25][Cbig=Cout]
-                b.pack(blk.conv.weight, p0, p1, Cin, Cout, True)
-                conv = (1, a16, dec_in_s[-1], p1, geom, fl)
-            else:
-                p1 = b.buf(f"dec{i}.p1", Cout * 25 * Cin)
-                p0 = b.buf(f"dec{i}.p0", Cin * 25 * Cout)
-                b.pack(blk.conv.weight, p0, p1, Cin, Cout, False)
-                conv = (1, "f32", dec_in[-1], p1, geom, fl)
-            # the last block feeds the final conv in fp32 (its 3-channel side runs on the VALU kernels of narrow.hip;
-            # measured: padding 3 -> 32 output columns for the MFMA halo kernel is LDS-read bound and 25 % slower)
-            nxt16 = i + 1 < L and dec16[i + 1]
-            u = None if nxt16 else b.buf(f"dec{i}.u", n_out)
-            u_s = b.sbuf(f"dec{i}.us", n_out) if nxt16 else None
-            saved = b.bn_fwd(fwd, f"dec{i}", tbuf, B * 4 * Hs * Hs, Cout, blk.bn, u, u_s, conv=conv)
-            dec_rec.append((blk, Cin, Cout, Hs, p0, tbuf, saved))
-            dec_in.append(u)
-            dec_in_s.append(u_s)
-        fin = dec.conv[L][0]
-        Cf = dec_ch[-1]
-        fl_fin = 50.0 * B * S * S * Cf * C
-        fp0 = b.buf("fin.p0", C * 25 * Cf)
-        fp1 = b.buf("fin.p1", Cf * 25 * C)
-        b.pack(fin.weight, fp0, fp1, C, Cf, False)
+        head = sections.EncoderHead(b, enc, B, blocks[-1].Cout)
+        head.fwd(fwd, blocks[-1].a)
+        head.latent(fwd, self.eps)
+        self.mu, self.logvar, self.z, self.kl = head.mu, head.logvar, head.z, head.kl
+        # (spare_p1, and shared_colsum_ws below: kept so that this plan's buffers and launches stay as they are)
+        trunk = sections.DecoderTrunk(b, dec, B, L, S, C, spare_p1=True)
+        fin, Cf = trunk.fin, trunk.ch[-1]
         xt_nhwc = b.buf("xt_nhwc", B * S * S * C)
-        if x3 and Cf == 64 and C in (1, 3):
-            # split-bf16 on the matrix cores, taps folded into the MFMA columns (the exact-f32 plan keeps the VALU kernel)
-            fwd.add("vp_conv5_smallout_bf16x3", P(dec_in[-1]), P(fp0), P(fin.bias), P(xt_nhwc), B, S, S, Cf, C, _ACT_SIGMOID,
-                    flops=fl_fin, tag="fin.fwd")
-        else:
-            b.conv5(fwd, 0, "f32", dec_in[-1], fp0, xt_nhwc, (B, S, S, Cf, C, 1), bias=fin.bias, act=_ACT_SIGMOID,
-                    flops=fl_fin, tag="fin.fwd")
+        dec_pass = trunk.fwd(fwd, "dec", self.z, xt_nhwc, "fin")
         self.recon = b.buf("recon", 1)
         self.kl_sum = b.buf("kl_sum", 1)
         n_pix = B * S * S * C
@@ -269,138 +138,36 @@ class FusedVAEStep:
         self.x_tilde = xt_nhwc.view(B, S, S, C).permute(0, 3, 1, 2)  # logical NCHW, channels_last memory
         fwd.hook("fwd_done")
 
-        # ---------------- backward ----------------
+        # ---------------- backward: the reverse walk ----------------
         inv_b = 1.0 / B
         dlogit = b.buf("g.dlogit", n_pix)
-        # final conv's input gradient: rows-in-K kernel of edge.hip (C = 1 | 3 image channels, 64 decoder channels), else the bf16x3
-        # halo kernel with dlogit padded to 8 channels
-        fin_rowk = x3 and Cf == 64 and C in (1, 3)
-        fin16 = x3 and Cf % 8 == 0 and C < 8 and not fin_rowk
-        if fin16:
-            dlogit_s = b.sbuf("g.dlogit_s", B * S * S * 8)
-            fp1s = b.sbuf("fin.p1s", Cf * 25 * 8)
-            b.pack(fin.weight, None, fp1s, C, Cf, True, 8, bf16=True)       # bf16 pairs: read by the halo kernel in every mode
-            bwd.add("vp_bce_sigmoid_bwd_pad_split_f32", P(xt_nhwc), P(x_nhwc), inv_b, P(dlogit), P(dlogit_s), B * S * S, C, 8)
+        if fin.dlogit_s is not None:      # the final conv's input gradient reads dlogit padded to 8 channels, as split planes
+            bwd.add("vp_bce_sigmoid_bwd_pad_split_f32", P(xt_nhwc), P(x_nhwc), inv_b, P(dlogit), P(fin.dlogit_s), B * S * S, C, 8)
         else:
             bwd.add("vp_bce_sigmoid_bwd_f32", P(xt_nhwc), P(x_nhwc), inv_b, P(dlogit), n_pix)
-        b.colsum(bwd, "g.fin", dlogit, grad_of(fin.bias), B * S * S, C, side=b.side_slot())
-        ws_wg = b.wgrad_workspace([(B, r[3], r[1], r[2]) for r in enc_rec] + [(B, r[3], r[2], r[1]) for r in dec_rec],
-                                  at_least=lib.vp_conv5_wgrad_workspace_bytes(B, S, S, Cf, C, 1))
-        n_tapm = lib.vp_conv5_smallout_wgrad_bf16x3_workspace_bytes(B, S, S, Cf, C)      # (the exact-f32 form takes the same slabs)
-        if n_tapm:      # on the matrix cores, taps folded into the MFMA rows (csrc/edge.hip); its own slab workspace
-            ws_fw = b.ws("g.finwgrad.ws", n_tapm)
-            bwd.add("vp_conv5_smallout_wgrad_bf16x3" if x3 else "vp_conv5_smallout_wgrad_f32", P(dec_in[-1]), P(dlogit), P(grad_of(fin.weight)),
-                    B, S, S, Cf, C, P(ws_fw), ws_fw.numel() * 4, flops=fl_fin, tag="fin.wgrad", side=b.side_slot())
-        else:
-            bwd.add("vp_conv5_wgrad_f32", P(dec_in[-1]), P(dlogit), P(grad_of(fin.weight)), B, S, S, Cf, C, 1, P(ws_wg), ws_wg.numel() * 4,
-                    flops=fl_fin, tag="fin.wgrad", side=b.side_slot())   # reads dlogit / dec_in[-1]: both live on
+        b.wgrad_workspace([(B, k.Hs, k.Cin, k.Cout) for k in blocks] + [(B, Hs, Cout, Cin) for Hs, Cin, Cout in trunk.layers],
+                          at_least=lib.vp_conv5_wgrad_workspace_bytes(B, S, S, Cf, C, 1))
         # two ping-pong gradient buffers sized for the largest activation
-        big = max([B * F0, B * F1, n_pix] + [B * 4 * r[3] * r[3] * r[2] for r in dec_rec] + [B * r[3] * r[3] * r[2] for r in enc_rec]
-                  + [B * S * S * Cf])
+        big = max([B * head.F0, B * trunk.F1, n_pix, B * S * S * Cf] + [B * 4 * Hs * Hs * Cout for Hs, _, Cout in trunk.layers]
+                  + [k.R * k.Cout for k in blocks])
         gA, gB = b.buf("g.A", big), b.buf("g.B", big)
-        if fin_rowk:
-            bwd.add("vp_conv5_smallin_dgrad_bf16x3", P(dlogit), P(fin.weight), P(gA), B, S, S, C, Cf, flops=fl_fin, tag="fin.dgrad")
-        elif fin16:
-            b.conv5(bwd, 1, "bf16x3", dlogit_s, fp1s, gA, (B, S, S, 8, Cf, 1), flops=fl_fin, tag="fin.dgrad")
-        elif Cf == 64 and C in (1, 3):    # exact fp32 on the same rows-in-K tiling (csrc/edge.hip dgrad_rowk_f32_kernel)
-            bwd.add("vp_conv5_smallin_dgrad_f32", P(dlogit), P(fin.weight), P(gA), B, S, S, C, Cf, flops=fl_fin, tag="fin.dgrad")
-        else:
-            b.conv5(bwd, 1, "f32", dlogit, fp1, gA, (B, S, S, C, Cf, 1), flops=fl_fin, tag="fin.dgrad")
-        cur, other = gA, gB
-        gS2 = b.grad_planes(big)          # split gradient (output of BN backward) for the 16-bit kernels
-        self._grad_planes = gS2 if x2 else []
-        for i in range(L - 1, -1, -1):
-            blk, Cin, Cout, Hs, p0, tbuf, saved = dec_rec[i]
-            R = B * 4 * Hs * Hs
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            geom = (B, Hs, Hs, Cout, Cin, 2)
-            if dec16[i]:
-                k, gS = b.next_plane(bwd)
-                b.bn_bwd(bwd, tbuf, cur, None, R, Cout, blk.bn, saved, gS)                      # gS = d t_i (split)
-                b.wgrad5(bwd, gS, dec_in_s[i], grad_of(blk.conv.weight), geom, k, flops=fl, tag=f"dec{i}.wgrad")
-                b.conv5(bwd, 0, a16, gS, p0, cur, geom, products=2, alpha=1.0 / GS, flops=fl, tag=f"dec{i}.dgrad")  # cur = d input_i
-            else:
-                b.bn_bwd(bwd, tbuf, cur, other, R, Cout, blk.bn, saved)                         # other = d t_i
-                bwd.add("vp_conv5_wgrad_f32", P(other), P(dec_in[i]), P(grad_of(blk.conv.weight)), *geom,
-                        P(ws_wg), ws_wg.numel() * 4, flops=fl, tag=f"dec{i}.wgrad")
-                b.conv5(bwd, 0, "f32", other, p0, cur, geom, flops=fl, tag=f"dec{i}.dgrad")     # cur = d input_i
-        bwd.add("vp_nhwc_to_nchw_f32", P(cur), P(other), B, dsize, 8, 8)                # other = d db  (B, F1)
-        b.bn_bwd(bwd, d, other, cur, B, F1, dfc_bn, d_saved)                           # cur = d d
-        b.lin_wgrad(bwd, cur, self.z, grad_of(dfc_lin.weight), B, F1, Z)
+        planes = b.grad_planes(big)       # split gradient (output of BN backward) for the 16-bit kernels
+        self._grad_planes = planes if b.x2 else []
         dz = b.buf("g.dz", B, Z)
-        b.lin_dgrad(bwd, cur, dfc_lin.weight, dz, B, F1, Z)
+        trunk.bwd(bwd, dec_pass, dlogit, gA, gB, dz=dz)
         # every decoder gradient is final and no decoder parameter is read any more: the data-parallel step may start
         # reducing that slice of the arena and the optimiser may update it
         bwd.hook("dec_done")
-        dmu, dlv = b.buf("g.dmu", B, Z), b.buf("g.dlv", B, Z)
-        bwd.add("vp_latent_bwd_f32", P(self.mu), P(self.logvar), P(self.eps), P(dz), None, inv_b, P(dmu), P(dlv), B, Z)
-        dhb_a, dhb_b = b.buf("g.dhb_a", B * 1024), b.buf("g.dhb_b", B * 1024)
-        for lin, dsrc, dst in ((enc.l_mu, dmu, dhb_a), (enc.l_var, dlv, dhb_b)):
-            b.lin_wgrad(bwd, dsrc, hb, grad_of(lin.weight), B, Z, 1024)
-            b.colsum(bwd, "g.heads", dsrc, grad_of(lin.bias), B, Z)
-            b.lin_dgrad(bwd, dsrc, lin.weight, dst, B, Z, 1024)
-        bwd.add("vp_add_f32", P(dhb_a), P(dhb_b), P(dhb_a), B * 1024)     # d hb = dgrad(mu head) + dgrad(logvar head)
-        dh = b.buf("g.dh", B * 1024)
-        b.bn_bwd(bwd, h, dhb_a, dh, B, 1024, fc_bn, h_saved)
-        # the factored multi-rank exchange and the one-rank outer-product Adam compute fc.0's weight gradient instead
-        bwd.hook("fc_wgrad", replaces_next=True)
-        b.lin_wgrad(bwd, dh, flat, grad_of(fc_lin.weight), B, 1024, F0)
-        self._fc_factors = (dh, flat, fc_lin.weight, F0)
-        b.lin_dgrad(bwd, dh, fc_lin.weight, gA, B, 1024, F0)
-        # the encoder's dense gradients (fc.0 = 134 MB at config 3, fc.1, l_mu, l_var) are final and its dense
-        # parameters are not read any more: second bucket
-        bwd.hook("enc_dense_done")
-        bwd.add("vp_nchw_to_nhwc_f32", P(gA), P(gB), B, size, 8, 8)
-        cur, other = gB, gA
+        head.bwd(bwd, self.eps, dz, inv_b, gA, gB, fc_wgrad_hook=True, shared_colsum_ws=True)
+        self._fc_factors = (head.dh, head.flat, head.fc_lin.weight, head.F0)
         # the encoder-tail bucket: its hook's index in the backward plan and the first of the blocks it covers (None: no such bucket)
         self._bwd_b_enc_tail = self._enc_tail_first = None
         for i in range(L - 1, -1, -1):
-            blk, Cin, Cout, Hs, p1, c, saved = enc_rec[i]
-            R = B * Hs * Hs
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            geom = (B, Hs, Hs, Cin, Cout, 2)
-            if i == 0 and enc0_cols:
-                xcol, KC = enc0
-                k, gS = b.next_plane(bwd)
-                b.bn_bwd(bwd, c, cur, None, R, Cout, blk.bn, saved, gS)  # gS = d c_0 (split)
-                dwc = b.buf("enc0.dwc", Cout * KC)
-                ws0 = b.ws("enc0.wgws", lib.vp_conv_wgrad_bf16x3_workspace_bytes(B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1))
-                # the LAST weight gradient of the step stays on the main stream: on the side stream the join that follows it (and
-                # precedes the optimiser) finds both queues idle for ~18 us -- the latency of a dependency between two hardware
-                # queues (profiles/r02_notes.md) -- while here the side stream has long finished when the main stream joins it
-                if x2:
-                    bwd.add("vp_conv_wgrad_f16x2", P(xcol), P(gS), P(dwc), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, 1.0 / GS, P(ws0), ws0.numel() * 4,
-                            flops=fl, tag="enc0.wgrad")
-                else:
-                    bwd.add("vp_conv_wgrad_bf16x3", P(xcol), P(gS), P(dwc), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, P(ws0), ws0.numel() * 4,
-                            flops=fl, tag="enc0.wgrad")
-                bwd.add("vp_unpack_dw_im2col5_f32", P(dwc), P(grad_of(blk.conv.weight)), Cout, Cin)
-            elif enc16[i]:
-                k, gS = b.next_plane(bwd)
-                b.bn_bwd(bwd, c, cur, None, R, Cout, blk.bn, saved, gS)  # gS = d c_i (split)
-                b.wgrad5(bwd, enc_in_s[i], gS, grad_of(blk.conv.weight), geom, k, flops=fl, tag=f"enc{i}.wgrad")
-                if i > 0:
-                    b.conv5(bwd, 1, a16, gS, p1, cur, (B, Hs, Hs, Cout, Cin, 2), products=2, alpha=1.0 / GS,
-                            flops=fl, tag=f"enc{i}.dgrad")                             # cur = d a_{i-1}
-                if i == max(L - 2, 1):
-                    # the gradients of encoder.conv[i:] (16.4 of the 17 MB of conv parameters at config 3) are issued: third bucket
-                    self._bwd_b_enc_tail, self._enc_tail_first = len(bwd.calls), i
-                    bwd.hook("enc_tail")
-            elif i == 0 and enc0_cols32:
-                xcol, KC = enc0
-                b.bn_bwd(bwd, c, cur, other, R, Cout, blk.bn, saved)            # other = d c_0
-                dwc = b.buf("enc0.dwc", Cout * KC)
-                ws0 = b.ws("enc0.wgws", lib.vp_conv_wgrad_workspace_bytes(B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1))
-                bwd.add("vp_conv_wgrad_f32", P(xcol), P(other), P(dwc), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, P(ws0), ws0.numel() * 4,
-                        flops=fl, tag="enc0.wgrad")
-                bwd.add("vp_unpack_dw_im2col5_f32", P(dwc), P(grad_of(blk.conv.weight)), Cout, Cin)
-            else:
-                b.bn_bwd(bwd, c, cur, other, R, Cout, blk.bn, saved)            # other = d c_i
-                # side stream only for the last layer of the walk (i == 0): nothing rewrites `other` after it
-                bwd.add("vp_conv5_wgrad_f32", P(enc_in[i]), P(other), P(grad_of(blk.conv.weight)), *geom,
-                        P(ws_wg), ws_wg.numel() * 4, flops=fl, tag=f"enc{i}.wgrad", side=(b.side_slot() if i == 0 else None))
-                if i > 0:
-                    b.conv5(bwd, 1, "f32", other, p1, cur, (B, Hs, Hs, Cout, Cin, 2), flops=fl, tag=f"enc{i}.dgrad")  # cur = d a_{i-1}
+            blocks[i].bwd(bwd, gB, gA)
+            if blocks[i].is16 and i == max(L - 2, 1):
+                # the gradients of encoder.conv[i:] (16.4 of the 17 MB of conv parameters at config 3) are issued: third bucket
+                self._bwd_b_enc_tail, self._enc_tail_first = len(bwd.calls), i
+                bwd.hook("enc_tail")
         b.finish(fwd)
         self._fwd, self._bwd = fwd, bwd
         self._bn_momentum_eps = {id(bn): (float(bn.momentum), float(bn.eps)) for bn, _ in b.bn_counts}

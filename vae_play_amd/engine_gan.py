@@ -28,7 +28,7 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
-from . import _lib, ops, parallel
+from . import _lib, ops, parallel, sections
 from .networks import VaeGan
 from .plan import PlanBuilder, _Plan, _ptr, grad_of, plan_device, side_ctx, sync_counters_on_state_dict
 
@@ -113,113 +113,40 @@ class FusedVAEGANStep:
         def grad2_of(p):         # second decoder pass: same offsets in the shadow arena
             return self._dec_shadow[p._vp_off:p._vp_off + p.numel()].view_as(p)
 
+        def require16(blocks, what):
+            # (the sections would route other widths to the fp32 kernels: a combination this step has never run)
+            if not all(k.is16 for k in blocks):
+                raise NotImplementedError(f"{what} widths must be multiples of 8")
+
         # =================================================== forward ===================================================
         self.xcat = b.buf("xcat", n3, 1, S, S)        # (original | reconstructed | sampled): the discriminator's batch
         self.eps, self.z_p = b.buf("eps", B, Z), b.buf("z_p", B, Z)
         self.targets = b.buf("targets", B, 3)
         xcat = self.xcat
 
-        # ---- encoder (models/networks.py:49-78) ----
-        enc_ch = [1] + [blk.conv.weight.shape[0] for blk in enc.conv]
-        enc_rec = []
-        in_s = None
-        for i, blk in enumerate(enc.conv):
+        # ---- encoder (models/networks.py:49-78): im2col stem over xcat[:B], gather blocks, head ----
+        if enc.conv[0].conv.weight.shape[0] % 8:
+            raise NotImplementedError("encoder width must be a multiple of 8")
+        enc_blocks = sections.gather_stack(b, "enc", enc.conv, B, S, None, None, image=xcat)
+        require16(enc_blocks, "encoder")
+        for i, blk in enumerate(enc_blocks):
             if i == 1 and b.k_pack is not None:
                 fwd.wait_side(b.k_pack)
-            Cin, Cout, Hs = enc_ch[i], enc_ch[i + 1], S >> (i + 1)
-            n_out = B * Hs * Hs * Cout
-            c = b.buf(f"enc{i}.c", n_out)
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            last = i == L - 1
-            a = b.buf(f"enc{i}.a", n_out) if last else None
-            a_s = None if last else b.sbuf(f"enc{i}.as", n_out)
-            if i == 0:
-                if Cout % 8:
-                    raise NotImplementedError("encoder width must be a multiple of 8")
-                KC = lib.vp_im2col5s2_cols(1)
-                xcol = b.sbuf("enc0.xcol", B * Hs * Hs * KC)
-                w0s = b.sbuf("enc0.w0s", Cout * KC)
-                fwd.add("vp_im2col5s2_split_f32", P(xcat), P(xcol), B, 1, S, S, 1)
-                fwd.add("vp_pack_w_im2col5_split", P(blk.conv.weight), P(w0s), Cout, 1)
-                fwd.add("vp_conv_gather_bf16x3", P(xcol), P(w0s), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE,
-                        flops=fl, tag="enc0.fwd")
-                saved = b.bn_fwd(fwd, "enc0", c, B * Hs * Hs, Cout, blk.bn, a, a_s)
-                enc_rec.append((blk, Cin, Cout, Hs, None, c, saved, (xcol, KC)))
-            else:
-                p0 = b.sbuf(f"enc{i}.p0s", Cout * 25 * Cin)
-                p1 = b.sbuf(f"enc{i}.p1s", Cin * 25 * Cout)
-                b.pack(blk.conv.weight, p0, p1, Cout, Cin, True)
-                saved = b.bn_fwd(fwd, f"enc{i}", c, B * Hs * Hs, Cout, blk.bn, a, a_s,
-                                 conv=(0, "bf16x3", in_s, p0, (B, Hs, Hs, Cin, Cout, 2), fl))
-                enc_rec.append((blk, Cin, Cout, Hs, p1, c, saved, in_s))
-            enc_last, in_s = a, a_s
+            blk.fwd(fwd)
         if L == 1 and b.k_pack is not None:
             fwd.wait_side(b.k_pack)
-        size = enc_ch[-1]
-        F0 = 64 * size
-        flat = b.buf("enc.flat", B * F0)
-        fwd.add("vp_nhwc_to_nchw_f32", P(enc_last), P(flat), B, size, 8, 8)
-        fc_lin, fc_bn = enc.fc[0], enc.fc[1]
-        H1 = fc_lin.weight.shape[0]
-        h, hb = b.buf("enc.h", B * H1), b.buf("enc.hb", B * H1)
-        b.lin_fwd(fwd, flat, fc_lin.weight, None, h, B, H1, F0)
-        h_saved = b.bn_fwd(fwd, "enc.fc", h, B, H1, fc_bn, hb)
-        self.mu, self.logvar = b.buf("mu", B, Z), b.buf("logvar", B, Z)
-        for lin, out in ((enc.l_mu, self.mu), (enc.l_var, self.logvar)):
-            b.lin_fwd(fwd, hb, lin.weight, lin.bias, out, B, Z, H1)
-        self.z, self.kl = b.buf("z", B, Z), b.buf("kl", B)
-        fwd.add("vp_latent_fwd_f32", P(self.mu), P(self.logvar), P(self.eps), P(self.z), P(self.kl), B, Z)
+        head = sections.EncoderHead(b, enc, B, enc_blocks[-1].Cout)
+        head.fwd(fwd, enc_blocks[-1].a)
+        head.latent(fwd, self.eps)
+        self.mu, self.logvar, self.z, self.kl = head.mu, head.logvar, head.z, head.kl
 
         # ---- decoder (models/networks.py:81-112), run on z and on z_p with the same packed weights ----
-        dfc_lin, dfc_bn = dec.fc[0], dec.fc[1]
-        dsize = dec._c0
-        F1 = 64 * dsize
-        dec_ch = [dsize] + [blk.conv.weight.shape[1] for blk in list(dec.conv)[:L]]
-        if any(ch % 8 for ch in dec_ch):
+        # (own_wgrad_ws, halo_dgrad: kept so that this plan's buffers and launches stay as they are)
+        trunk = sections.DecoderTrunk(b, dec, B, L, S, 1, own_wgrad_ws=True, halo_dgrad=False)
+        if any(ch % 8 for ch in trunk.ch):
             raise NotImplementedError("decoder widths must be multiples of 8")
-        dec_pk = []
-        for i in range(L):
-            blk = dec.conv[i]
-            Cin, Cout = dec_ch[i], dec_ch[i + 1]
-            p1 = b.sbuf(f"dec{i}.p1s", Cout * 25 * Cin)      # T family: [Cbig = Cout][25][Csmall = Cin]
-            p0 = b.sbuf(f"dec{i}.p0s", Cin * 25 * Cout)      # F family (input gradient): [Csmall = Cin][25][Cbig = Cout]
-            b.pack(blk.conv.weight, p0, p1, Cin, Cout, True)
-            dec_pk.append((p0, p1))
-        fin = dec.conv[L][0]
-        Cf = dec_ch[-1]
-        fin_edge = Cf == 64
-        fp0 = b.buf("fin.p0", 25 * Cf)
-        fp1 = None if fin_edge else b.buf("fin.p1", Cf * 25)
-        b.pack(fin.weight, fp0, fp1, 1, Cf, False)
-
-        def dec_fwd(tag, zbuf, out_ptr):
-            d, db = b.buf(f"{tag}.d", B * F1), b.buf(f"{tag}.db", B * F1)
-            b.lin_fwd(fwd, zbuf, dfc_lin.weight, None, d, B, F1, Z)
-            fc_rec = b.bn_fwd(fwd, f"{tag}.fc", d, B, F1, dfc_bn, db)
-            dn_s = b.sbuf(f"{tag}.in_s", B * F1)
-            fwd.add("vp_nchw_to_nhwc_split_f32", P(db), None, P(dn_s), B, dsize, 8, 8)
-            cur_s, recs, u = dn_s, [], None
-            for i in range(L):
-                blk = dec.conv[i]
-                Cin, Cout, Hs = dec_ch[i], dec_ch[i + 1], 8 << i
-                n_out = B * 4 * Hs * Hs * Cout
-                tbuf = b.buf(f"{tag}{i}.t", n_out)
-                fl = 50.0 * B * Hs * Hs * Cin * Cout
-                last = i == L - 1
-                u = b.buf(f"{tag}{i}.u", n_out) if last else None
-                u_s = None if last else b.sbuf(f"{tag}{i}.us", n_out)
-                saved = b.bn_fwd(fwd, f"{tag}{i}", tbuf, B * 4 * Hs * Hs, Cout, blk.bn, u, u_s,
-                                 conv=(1, "bf16x3", cur_s, dec_pk[i][1], (B, Hs, Hs, Cin, Cout, 2), fl))
-                recs.append((blk, Cin, Cout, Hs, dec_pk[i][0], tbuf, saved, cur_s))
-                cur_s = u_s
-            flf = 50.0 * B * S * S * Cf
-            if fin_edge:
-                fwd.add("vp_conv5_smallout_bf16x3", P(u), P(fp0), P(fin.bias), out_ptr, B, S, S, Cf, 1, _ACT_SIGMOID, flops=flf, tag=f"{tag}.fin.fwd")
-            else:
-                fwd.add("vp_conv5_gather_f32", P(u), P(fp0), P(fin.bias), out_ptr, B, S, S, Cf, 1, 1, _ACT_SIGMOID, flops=flf, tag=f"{tag}.fin.fwd")
-            return {"tag": tag, "z": zbuf, "d": d, "fc": fc_rec, "blocks": recs, "u": u, "out": out_ptr}
-
-        dec1 = dec_fwd("dec", self.z, at(xcat, n_pix))            # x_tilde = xcat[B:2B]
+        Cf = trunk.ch[-1]
+        dec1 = trunk.fwd(fwd, "dec", self.z, at(xcat, n_pix), "dec.fin")            # x_tilde = xcat[B:2B]
 
         # ---- param_encoder (DirectDecoder, models/networks.py:118-148): bias-ed Linear layers without activations ----
         pe_rec = []
@@ -243,7 +170,7 @@ class FusedVAEGANStep:
         d_r, d_xy = b.buf("g.d_r", B * n_r), b.buf("g.d_xy", B * n_xy)
         fwd.add("vp_smooth_l1_cat_f32", P(self.targets), P(self.p_r), P(self.p_xy), B, n_r, n_xy, 1.0 / B, P(self.l1), P(d_r), P(d_xy))
 
-        dec2 = dec_fwd("decp", self.z_p, at(xcat, 2 * n_pix))     # x_p = xcat[2B:3B]
+        dec2 = trunk.fwd(fwd, "decp", self.z_p, at(xcat, 2 * n_pix), "decp.fin")    # x_p = xcat[2B:3B]
 
         # ---- discriminator on (x | x_tilde | x_p) (models/networks.py:151-198), one pass for "REC" and "GAN" ----
         conv0 = disc.conv[0][0]
@@ -255,32 +182,18 @@ class FusedVAEGANStep:
         fwd_disc.add("vp_conv5_smallin_fwd_bf16x3", P(xcat), P(conv0.weight), P(conv0.bias), P(y0), n3, S, S, 1, C0, _ACT_RELU,
                      flops=50.0 * n3 * S * S * C0, tag="disc0.fwd")
         fwd_disc.add("vp_split_f32", P(y0), P(y0s), n3 * S * S * C0)
-        disc_ch = [C0] + [blk.conv.weight.shape[0] for blk in list(disc.conv)[1:]]
-        disc_rec = []
-        in_s = y0s
-        self._disc_replay = []
-        for i in range(1, L + 1):
-            blk = disc.conv[i]
-            Cin, Cout, Hs = disc_ch[i - 1], disc_ch[i], S >> i
-            n_out = n3 * Hs * Hs * Cout
-            c = b.buf(f"disc{i}.c", n_out)
-            fl = 50.0 * n3 * Hs * Hs * Cin * Cout
-            last = i == L
-            a = b.buf(f"disc{i}.a", n_out) if last else None
-            a_s = None if last else b.sbuf(f"disc{i}.as", n_out)
-            p0 = b.sbuf(f"disc{i}.p0s", Cout * 25 * Cin)
-            p1 = b.sbuf(f"disc{i}.p1s", Cin * 25 * Cout)
-            b.pack(blk.conv.weight, p0, p1, Cout, Cin, True)
-            saved = b.bn_fwd(fwd_disc, f"disc{i}", c, n3 * Hs * Hs, Cout, blk.bn, a, a_s, count=2,
-                             conv=(0, "bf16x3", in_s, p0, (n3, Hs, Hs, Cin, Cout, 2), fl))
-            self._disc_replay.append(blk.bn)
-            disc_rec.append((blk, Cin, Cout, Hs, p1, c, saved, in_s))
-            disc_last, in_s = a, a_s
-        Cd = disc_ch[-1]
+        # (count=2: the reference runs these blocks twice per step)
+        disc_blocks = sections.gather_stack(b, "disc", list(disc.conv)[1:], n3, S, None, y0s, count=2, first_index=1)
+        require16(disc_blocks, "discriminator")
+        for blk in disc_blocks:
+            blk.fwd(fwd_disc)
+        self._disc_replay = [blk.bn for blk in disc_blocks]
+        last = disc_blocks[-1]
+        Cd = last.Cout
         nf = 64 * Cd                                               # features per image at the tap
-        tap = disc_rec[-1][5]                                      # pre-BatchNorm output of the last block: "disc_layer"
+        tap = last.c                                               # pre-BatchNorm output of the last block: "disc_layer"
         dflat = b.buf("disc.flat", n3 * nf)
-        fwd_disc.add("vp_nhwc_to_nchw_f32", P(disc_last), P(dflat), n3, Cd, 8, 8)
+        fwd_disc.add("vp_nhwc_to_nchw_f32", P(last.a), P(dflat), n3, Cd, 8, 8)
         dl0, dl_bn, dl3 = disc.fc[0], disc.fc[1], disc.fc[3]
         Hd = dl0.weight.shape[0]
         dh, dhb = b.buf("disc.h", n3 * Hd), b.buf("disc.hb", n3 * Hd)
@@ -303,26 +216,14 @@ class FusedVAEGANStep:
         self.disc_layer_nhwc = tap.view(n3, 8, 8, Cd)
 
         # =================================================== backward ===================================================
-        big_d = max([n3 * S * S * C0] + [n3 * r[3] * r[3] * r[2] for r in disc_rec] + [n3 * nf])
-        big_v = max([B * F0, B * F1, n_pix * Cf] + [B * 4 * r[3] * r[3] * r[2] for r in dec1["blocks"]] + [B * r[3] * r[3] * r[2] for r in enc_rec])
+        dec_acts = [B * 4 * Hs * Hs * Cout for Hs, _, Cout in trunk.layers]
+        big_d = max([n3 * S * S * C0] + [k.R * k.Cout for k in disc_blocks] + [n3 * nf])
+        big_v = max([B * head.F0, B * trunk.F1, n_pix * Cf] + dec_acts + [k.R * k.Cout for k in enc_blocks])
         gA, gB = b.buf("g.A", big_d), b.buf("g.B", big_d)          # discriminator phase
         hA, hB = b.buf("g.hA", big_v), b.buf("g.hB", big_v)        # decoder / encoder phases
-        b.grad_planes(max([n3 * r[3] * r[3] * r[2] for r in disc_rec] + [B * 4 * r[3] * r[3] * r[2] for r in dec1["blocks"]]
-                          + [B * r[3] * r[3] * r[2] for r in enc_rec]))
-        b.wgrad_workspace([(n3, r[3], r[1], r[2]) for r in disc_rec] + [(B, r[3], r[1], r[2]) for r in enc_rec[1:]]
-                          + [(B, r[3], r[2], r[1]) for r in dec1["blocks"]])
-
-        def gather_block_bwd(rec, Bn, cur, tag, pre_split=None):
-            """conv5x5 s2 + BatchNorm + ReLU block, dy in ``cur`` (fp32 NHWC) -> dx in ``cur``"""
-            blk, Cin, Cout, Hs, p1, c, saved, in_s = rec
-            fl = 50.0 * Bn * Hs * Hs * Cin * Cout
-            k, gS = b.next_plane(bwd)
-            if pre_split is None:
-                b.bn_bwd(bwd, c, cur, None, Bn * Hs * Hs, Cout, blk.bn, saved, gS)
-            else:
-                pre_split(gS)
-            b.wgrad5(bwd, in_s, gS, grad_of(blk.conv.weight), (Bn, Hs, Hs, Cin, Cout, 2), k, flops=fl, tag=f"{tag}.wgrad")
-            b.conv5(bwd, 1, "bf16x3", gS, p1, cur, (Bn, Hs, Hs, Cout, Cin, 2), flops=fl, tag=f"{tag}.dgrad")
+        b.grad_planes(max([k.R * k.Cout for k in disc_blocks + enc_blocks] + dec_acts))
+        b.wgrad_workspace([(k.Bn, k.Hs, k.Cin, k.Cout) for k in disc_blocks + enc_blocks[1:]]
+                          + [(B, Hs, Cout, Cin) for Hs, Cin, Cout in trunk.layers])
 
         # ---- discriminator head ----
         b.lin_wgrad(bwd, dlogit, dhb, grad_of(dl3.weight), n3, 1, Hd)
@@ -334,19 +235,17 @@ class FusedVAEGANStep:
         b.lin_dgrad(bwd, g_h, dl0.weight, gA, n3, Hd, nf)
         bwd.add("vp_nchw_to_nhwc_f32", P(gA), P(gB), n3, Cd, 8, 8)         # gB = d (last block's activation)
         # ---- last block: its pre-BatchNorm output also feeds the feature loss (1 + lambda) * sum(mse) ----
-        g_mse = torch.full((B,), self.c_mse, dtype=torch.float32, device=self.dev)
-        self._bufs["g.c_mse"] = g_mse
+        g_mse = b.buf("g.c_mse", B).fill_(self.c_mse)
         m_ab = b.buf("g.mse_ab", 2 * B * nf)
-        blk, Cin, Cout, Hs, p1, c, saved, in_s_l = disc_rec[-1]
 
         def tap_split(gS):
-            b.bn_bwd(bwd, c, gB, gA, n3 * Hs * Hs, Cout, blk.bn, saved)                                 # gA = BatchNorm path
+            b.bn_bwd(bwd, tap, gB, gA, last.R, last.Cout, last.bn, last.saved)                          # gA = BatchNorm path
             bwd.add("vp_half_sqdiff_bwd_f32", P(tap), at(tap, B * nf), P(g_mse), P(m_ab), at(m_ab, B * nf), B, nf, 1)
             bwd.add("vp_add_f32", P(gA), P(m_ab), P(gA), 2 * B * nf)                              # + feature loss (original, reconstructed)
             bwd.add("vp_split_f32", P(gA), P(gS), n3 * nf)
-        gather_block_bwd(disc_rec[-1], n3, gB, f"disc{L}", pre_split=tap_split)
-        for i in range(L - 1, 0, -1):
-            gather_block_bwd(disc_rec[i - 1], n3, gB, f"disc{i}")
+        last.bwd(bwd, gB, gA, pre_split=tap_split)
+        for blk in reversed(disc_blocks[:-1]):
+            blk.bwd(bwd, gB, gA)
         # ---- stem: conv 1 -> C0 + bias + ReLU (ReLU in the convolution's epilogue) ----
         n0 = n3 * S * S * C0
         bwd.add("vp_act_bwd_from_y_f32", P(y0), P(gB), P(gA), n0, _ACT_RELU, 0.0)                  # gA = d (conv output)
@@ -363,39 +262,11 @@ class FusedVAEGANStep:
         bwd.hook("disc_done")       # every discriminator gradient is launched and none of its parameters is read again in this step
 
         # ---- decoder ----
-        def dec_bwd(rec, dout, gfn, dz):
+        def dec_bwd(ps, dout, gfn, dz):
             """``dout`` = pointer to the gradient w.r.t. the sigmoid output (fp32, B*S*S); writes d z into ``dz`` when given"""
-            tag = rec["tag"]
-            dlg = b.buf(f"g.{tag}.dlogit", n_pix)
-            bwd.add("vp_act_bwd_from_y_f32", rec["out"], dout, P(dlg), n_pix, _ACT_SIGMOID, 0.0)
-            b.colsum(bwd, f"{tag}.finb", dlg, gfn(fin.bias), n_pix, 1, side=b.side_slot())
-            flf = 50.0 * B * S * S * Cf
-            nb = lib.vp_conv5_smallout_wgrad_bf16x3_workspace_bytes(B, S, S, Cf, 1) if fin_edge else 0  # 0: outside the taps-in-M kernel
-            if nb:
-                wsf = b.ws(f"{tag}.finwg.ws", nb)
-                bwd.add("vp_conv5_smallout_wgrad_bf16x3", P(rec["u"]), P(dlg), P(gfn(fin.weight)), B, S, S, Cf, 1, P(wsf), wsf.numel() * 4,
-                        flops=flf, tag=f"{tag}.fin.wgrad", side=b.side_slot())
-            else:
-                wsf = b.ws(f"{tag}.finwg.ws", lib.vp_conv5_wgrad_workspace_bytes(B, S, S, Cf, 1, 1))
-                bwd.add("vp_conv5_wgrad_f32", P(rec["u"]), P(dlg), P(gfn(fin.weight)), B, S, S, Cf, 1, 1, P(wsf), wsf.numel() * 4,
-                        flops=flf, tag=f"{tag}.fin.wgrad", side=b.side_slot())
-            if fin_edge:
-                bwd.add("vp_conv5_smallin_dgrad_bf16x3", P(dlg), P(fin.weight), P(hA), B, S, S, 1, Cf, flops=flf, tag=f"{tag}.fin.dgrad")
-            else:
-                b.conv5(bwd, 1, "f32", dlg, fp1, hA, (B, S, S, 1, Cf, 1), flops=flf, tag=f"{tag}.fin.dgrad")
-            for i in range(L - 1, -1, -1):
-                blk, Cin, Cout, Hs, p0, tbuf, saved, in_s = rec["blocks"][i]
-                fl = 50.0 * B * Hs * Hs * Cin * Cout
-                geom = (B, Hs, Hs, Cout, Cin, 2)
-                k, gS = b.next_plane(bwd)
-                b.bn_bwd(bwd, tbuf, hA, None, B * 4 * Hs * Hs, Cout, blk.bn, saved, gS, gfn=gfn)
-                b.wgrad5(bwd, gS, in_s, gfn(blk.conv.weight), geom, k, flops=fl, tag=f"{tag}{i}.wgrad")
-                b.conv5(bwd, 0, "bf16x3", gS, p0, hA, geom, flops=fl, tag=f"{tag}{i}.dgrad")
-            bwd.add("vp_nhwc_to_nchw_f32", P(hA), P(hB), B, dsize, 8, 8)                             # hB = d db (B, F1)
-            b.bn_bwd(bwd, rec["d"], hB, hA, B, F1, dfc_bn, rec["fc"], gfn=gfn)                        # hA = d d
-            b.lin_wgrad(bwd, hA, rec["z"], gfn(dfc_lin.weight), B, F1, Z)
-            if dz is not None:
-                b.lin_dgrad(bwd, hA, dfc_lin.weight, dz, B, F1, Z)
+            dlg = b.buf(f"g.{ps.tag}.dlogit", n_pix)
+            bwd.add("vp_act_bwd_from_y_f32", ps.out, dout, P(dlg), n_pix, _ACT_SIGMOID, 0.0)
+            trunk.bwd(bwd, ps, dlg, hA, hB, gfn, dz)
 
         # second pass first (x_p: only the discriminator's gradient reaches it), into the shadow arena
         dec_bwd(dec2, at(dxc, n_pix), grad2_of, None)
@@ -417,8 +288,7 @@ class FusedVAEGANStep:
         for j in range(len(pe.head) - 1, -1, -1):
             dz_pe = pe_bwd(f"head{j}", dz_pe)
         # ---- first decoder pass: d x_tilde = discriminator part + reconstruction loss mean((x - x_tilde)^2) (train.py:61) ----
-        g_rec = torch.full((1,), 2.0 / n_pix, dtype=torch.float32, device=self.dev)
-        self._bufs["g.c_rec"] = g_rec
+        g_rec = b.buf("g.c_rec", 1).fill_(2.0 / n_pix)
         dxt = b.buf("g.dxt", n_pix)
         bwd.add("vp_half_sqdiff_bwd_f32", P(xcat), at(xcat, n_pix), P(g_rec), None, P(dxt), 1, n_pix, 1)     # 2/n (x_tilde - x)
         bwd.add("vp_add_f32", P(dxt), P(dxc), P(dxt), n_pix)
@@ -428,31 +298,10 @@ class FusedVAEGANStep:
         dz = b.buf("g.dz", B * Z)
         bwd.add("vp_add_f32", P(dz_dec), P(dz_pe), P(dz), B * Z)
 
-        # ---- encoder ----
-        dmu, dlv = b.buf("g.dmu", B, Z), b.buf("g.dlv", B, Z)
-        bwd.add("vp_latent_bwd_f32", P(self.mu), P(self.logvar), P(self.eps), P(dz), None, 1.0, P(dmu), P(dlv), B, Z)
-        dhb_a, dhb_b = b.buf("g.dhb_a", B * H1), b.buf("g.dhb_b", B * H1)
-        for lin, dsrc, dst in ((enc.l_mu, dmu, dhb_a), (enc.l_var, dlv, dhb_b)):
-            b.lin_wgrad(bwd, dsrc, hb, grad_of(lin.weight), B, Z, H1)
-            b.colsum(bwd, f"enc.{'mu' if lin is enc.l_mu else 'var'}", dsrc, grad_of(lin.bias), B, Z)
-            b.lin_dgrad(bwd, dsrc, lin.weight, dst, B, Z, H1)
-        bwd.add("vp_add_f32", P(dhb_a), P(dhb_b), P(dhb_a), B * H1)
-        g_eh = b.buf("g.enc_h", B * H1)
-        b.bn_bwd(bwd, h, dhb_a, g_eh, B, H1, fc_bn, h_saved)
-        b.lin_wgrad(bwd, g_eh, flat, grad_of(fc_lin.weight), B, H1, F0)
-        b.lin_dgrad(bwd, g_eh, fc_lin.weight, hA, B, H1, F0)
-        bwd.hook("enc_dense_done")  # the encoder's dense gradients (fc, l_mu, l_var) are launched, their parameters not read again
-        bwd.add("vp_nchw_to_nhwc_f32", P(hA), P(hB), B, size, 8, 8)
-        for i in range(L - 1, 0, -1):
-            gather_block_bwd(enc_rec[i], B, hB, f"enc{i}")
-        blk, Cin, Cout, Hs, _, c, saved, (xcol, KC) = enc_rec[0]
-        k, gS = b.next_plane(bwd)
-        b.bn_bwd(bwd, c, hB, None, B * Hs * Hs, Cout, blk.bn, saved, gS)
-        dwc = b.buf("enc0.dwc", Cout * KC)
-        ws0 = b.ws("enc0.wgws", lib.vp_conv_wgrad_bf16x3_workspace_bytes(B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1))
-        bwd.add("vp_conv_wgrad_bf16x3", P(xcol), P(gS), P(dwc), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, P(ws0), ws0.numel() * 4,
-                flops=50.0 * B * Hs * Hs * Cout, tag="enc0.wgrad")
-        bwd.add("vp_unpack_dw_im2col5_f32", P(dwc), P(grad_of(blk.conv.weight)), Cout, 1)
+        # ---- encoder: head (the KL term is not averaged over the batch here), gather blocks, stem ----
+        head.bwd(bwd, self.eps, dz, 1.0, hA, hB)
+        for blk in reversed(enc_blocks):
+            blk.bwd(bwd, hB, hA)
 
         b.finish(fwd)
         self._fwd, self._fwd_disc, self._bwd = fwd, fwd_disc, bwd

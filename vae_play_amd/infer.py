@@ -19,10 +19,8 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, sections
 from .plan import PlanBuilder, _Plan, _ptr, plan_device
-
-_ACT_NONE, _ACT_SIGMOID = ops.ACT_NONE, ops.ACT_SIGMOID
 
 
 class FusedVAEInference:
@@ -77,130 +75,33 @@ class FusedVAEInference:
         prep, p_enc, p_lat, p_dec = _Plan(), _Plan(), _Plan(), _Plan()
         P = _ptr
         b = PlanBuilder(self, self.dev, self.precision, side_on=False, wgrad_cus=(0, 0))
-        lib = b.lib
-        x3 = b.x3
-        a16 = self.precision
 
-        def use16(cin, cout):
-            return x3 and cin % 8 == 0 and cout % 8 == 0
-
-        # ---------------- encoder ----------------
+        # ---------------- encoder: stem / gather blocks in eval form -> head ----------------
         self.x_nchw = b.buf("x_nchw", B, C, S, S)
         self.eps = b.buf("eps", B, Z)
-        enc_ch = [C] + [blk.conv.weight.shape[0] for blk in enc.conv]
-        sp = [S // (2 ** i) for i in range(L + 1)]
-        enc16 = [use16(enc_ch[i], enc_ch[i + 1]) for i in range(L)]
-        enc0_cols = x3 and C in (1, 3) and enc_ch[1] % 8 == 0
-        enc0_cols32 = (not x3) and C in (1, 3) and enc_ch[1] % 16 == 0
-        if C > 1 and not (enc0_cols or enc0_cols32):
+        first = enc.conv[0].conv.weight
+        if C > 1 and not sections.Im2colStem.applies(b, C, first.shape[0]):
             x_nhwc = b.buf("x_nhwc", B * S * S * C)
             p_enc.add("vp_nchw_to_nhwc_f32", P(self.x_nchw), P(x_nhwc), B, C, S, S)
         else:
             x_nhwc = self.x_nchw          # one channel: the same memory order (the im2col kernels read NCHW themselves)
-        cur, cur_s = x_nhwc, None          # fp32 / split input of the next block
-        self.fused_layers, self.unfused_layers = [], []
-        for i, blk in enumerate(enc.conv):
-            Cin, Cout, Hs = enc_ch[i], enc_ch[i + 1], sp[i + 1]
-            n_out = B * Hs * Hs * Cout
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            geom = (B, Hs, Hs, Cin, Cout, 2)
-            tag = f"enc{i}"
-            folded = b.bn_fold(prep, tag, blk.bn)
-            nxt16 = i + 1 < L and enc16[i + 1]
-            a = None if nxt16 else b.buf(f"{tag}.a", n_out)
-            a_s = b.sbuf(f"{tag}.as", n_out) if nxt16 else None
-            if i == 0 and (enc0_cols or enc0_cols32):
-                # first block (1 or 3 image channels): a 1x1 layer over the materialised im2col, BatchNorm as its own pass
-                KC = lib.vp_im2col5s2_cols(Cin)
-                c = b.buf(f"{tag}.c", n_out)
-                if enc0_cols:
-                    xcol, w0 = b.sbuf("enc0.xcol", B * Hs * Hs * KC), b.sbuf("enc0.w0s", Cout * KC)
-                    prep.add("vp_pack_w_im2col5_split", P(blk.conv.weight), P(w0), Cout, Cin)
-                    p_enc.add("vp_im2col5s2_split_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1)
-                    p_enc.add("vp_conv_gather_bf16x3", P(xcol), P(w0), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE,
-                              flops=fl, tag=f"{tag}.fwd")
-                else:
-                    xcol, w0 = b.buf("enc0.xcol32", B * Hs * Hs * KC), b.buf("enc0.w0", Cout * KC)
-                    prep.add("vp_pack_w_im2col5_f32", P(blk.conv.weight), P(w0), Cout, Cin)
-                    p_enc.add("vp_im2col5s2_f32", P(self.x_nchw), P(xcol), B, Cin, S, S, 1)
-                    p_enc.add("vp_conv_gather_f32", P(xcol), P(w0), None, P(c), B, Hs, Hs, Hs, Hs, KC, Cout, 1, 1, _ACT_NONE,
-                              flops=fl, tag=f"{tag}.fwd")
-                b.bn_eval(p_enc, tag, c, B * Hs * Hs, Cout, blk.bn, folded[2], a, a_s)
-                self.unfused_layers.append(tag)
-            else:
-                if enc16[i]:
-                    w = b.sbuf(f"{tag}.p0s", Cout * 25 * Cin)
-                    b.pack(blk.conv.weight, w, None, Cout, Cin, True)
-                    arith, src = a16, cur_s
-                else:
-                    w = b.buf(f"{tag}.p0", Cout * 25 * Cin)
-                    b.pack(blk.conv.weight, w, None, Cout, Cin, False)
-                    arith, src = "f32", cur
-                fused = b.conv5_bn_eval(p_enc, tag, 0, arith, src, w, geom, blk.bn, folded, a, a_s, flops=fl)
-                (self.fused_layers if fused else self.unfused_layers).append(tag)
-            cur, cur_s = a, a_s
-        size = enc_ch[-1]
-        F0 = 64 * size
-        flat = b.buf("enc.flat", B * F0)
-        p_enc.add("vp_nhwc_to_nchw_f32", P(cur), P(flat), B, size, 8, 8)
-        fc_lin, fc_bn = enc.fc[0], enc.fc[1]
-        h, hb = b.buf("enc.h", B * 1024), b.buf("enc.hb", B * 1024)
-        b.lin_fwd(p_enc, flat, fc_lin.weight, None, h, B, 1024, F0)
-        b.bn_eval(p_enc, "enc.fc", h, B, 1024, fc_bn, b.bn_fold(prep, "enc.fc", fc_bn)[2], hb)
-        self.mu, self.logvar = b.buf("mu", B, Z), b.buf("logvar", B, Z)
-        for lin, out in ((enc.l_mu, self.mu), (enc.l_var, self.logvar)):
-            b.lin_fwd(p_enc, hb, lin.weight, lin.bias, out, B, Z, 1024)
+        blocks = sections.gather_stack(b, "enc", enc.conv, B, S, x_nhwc, None, image=self.x_nchw, train=False)
+        for blk in blocks:
+            blk.fwd_eval(p_enc, prep)
+        head = sections.EncoderHead(b, enc, B, blocks[-1].Cout)
+        head.fwd(p_enc, blocks[-1].a, prep)
+        self.mu, self.logvar, self.z = head.mu, head.logvar, head.z
 
         # ---------------- latent: z = eps * exp(logvar / 2) + mu ----------------
-        self.z = b.buf("z", B, Z)
-        p_lat.add("vp_latent_fwd_f32", P(self.mu), P(self.logvar), P(self.eps), P(self.z), None, B, Z)
+        head.latent(p_lat, self.eps, kl=False)
 
-        # ---------------- decoder ----------------
-        dfc_lin, dfc_bn = dec.fc[0], dec.fc[1]
-        dsize = dec._c0
-        F1 = 64 * dsize
-        d, db = b.buf("dec.d", B * F1), b.buf("dec.db", B * F1)
-        b.lin_fwd(p_dec, self.z, dfc_lin.weight, None, d, B, F1, Z)
-        b.bn_eval(p_dec, "dec.fc", d, B, F1, dfc_bn, b.bn_fold(prep, "dec.fc", dfc_bn)[2], db)
-        dec_ch = [dsize] + [blk.conv.weight.shape[1] for blk in list(dec.conv)[:L]]
-        dec16 = [use16(dec_ch[i], dec_ch[i + 1]) for i in range(L)]
-        cur = None if dec16[0] else b.buf("dec.in", B * F1)
-        cur_s = b.sbuf("dec.in_s", B * F1) if dec16[0] else None
-        p_dec.add("vp_nchw_to_nhwc_split_f32", P(db), P(cur), P(cur_s), B, dsize, 8, 8)
-        for i in range(L):
-            blk = dec.conv[i]
-            Cin, Cout, Hs = dec_ch[i], dec_ch[i + 1], 8 * (2 ** i)
-            n_out = B * 4 * Hs * Hs * Cout
-            fl = 50.0 * B * Hs * Hs * Cin * Cout
-            geom = (B, Hs, Hs, Cin, Cout, 2)
-            tag = f"dec{i}"
-            folded = b.bn_fold(prep, tag, blk.bn)
-            # the last block feeds the final convolution, which reads fp32
-            nxt16 = i + 1 < L and dec16[i + 1]
-            u = None if nxt16 else b.buf(f"{tag}.u", n_out)
-            u_s = b.sbuf(f"{tag}.us", n_out) if nxt16 else None
-            if dec16[i]:
-                w = b.sbuf(f"{tag}.p1s", Cout * 25 * Cin)       # scatter family: [Cbig = Cout][25][Csmall = Cin]
-                b.pack(blk.conv.weight, None, w, Cin, Cout, True)
-                arith, src = a16, cur_s
-            else:
-                w = b.buf(f"{tag}.p1", Cout * 25 * Cin)
-                b.pack(blk.conv.weight, None, w, Cin, Cout, False)
-                arith, src = "f32", cur
-            fused = b.conv5_bn_eval(p_dec, tag, 1, arith, src, w, geom, blk.bn, folded, u, u_s, flops=fl)
-            (self.fused_layers if fused else self.unfused_layers).append(tag)
-            cur, cur_s = u, u_s
-        fin = dec.conv[L][0]
-        Cf = dec_ch[-1]
-        fl_fin = 50.0 * B * S * S * Cf * C
-        fp0 = b.buf("fin.p0", C * 25 * Cf)
-        b.pack(fin.weight, fp0, None, C, Cf, False)
+        # ---------------- decoder: trunk in eval form ----------------
+        trunk = sections.DecoderTrunk(b, dec, B, L, S, C, train=False)
         xt_nhwc = b.buf("xt_nhwc", B * S * S * C)
-        if x3 and Cf == 64 and C in (1, 3):
-            p_dec.add("vp_conv5_smallout_bf16x3", P(cur), P(fp0), P(fin.bias), P(xt_nhwc), B, S, S, Cf, C, _ACT_SIGMOID,
-                      flops=fl_fin, tag="fin.fwd")
-        else:
-            b.conv5(p_dec, 0, "f32", cur, fp0, xt_nhwc, (B, S, S, Cf, C, 1), bias=fin.bias, act=_ACT_SIGMOID, flops=fl_fin, tag="fin.fwd")
+        dec_pass = trunk.fwd(p_dec, "dec", self.z, xt_nhwc, "fin", prep)
+        # a block is ONE launch where the library fuses the folded BatchNorm into the convolution's epilogue
+        self.fused_layers = [k.tag for k in blocks + dec_pass.blocks if k.fused]
+        self.unfused_layers = [k.tag for k in blocks + dec_pass.blocks if not k.fused]
         if C > 1:
             self.x_tilde = b.buf("x_tilde", B, C, S, S)
             p_dec.add("vp_nhwc_to_nchw_f32", P(xt_nhwc), P(self.x_tilde), B, C, S, S)

@@ -1,10 +1,11 @@
-"""Plan-building code shared by the fused training steps (engine.FusedVAEStep, engine_gan.FusedVAEGANStep).
+"""Plan-building code shared by the fused plans (engine.FusedVAEStep, engine_gan.FusedVAEGANStep, infer.FusedVAEInference).
 
 A fused step is a fixed list of HIP launches built once for a (model, batch size) pair and replayed every step:
   * ``_Plan``: the launch list and its runner (the per-step host path), with side-stream launches, waits and named hooks;
   * ``_SideCtx``: the side stream the weight gradients run on underneath the main chain;
-  * ``PlanBuilder``: the vocabulary both steps state their plans in -- buffers, weight packs, BatchNorm, dense layers, column
+  * ``PlanBuilder``: the vocabulary the plans are stated in -- buffers, weight packs, BatchNorm, dense layers, column
     sums, 5x5 weight gradients with their CU budget, side slots and the rotation of the split gradient planes.
+The sentences written in that vocabulary -- stem, stride-2 blocks, encoder head, decoder trunk, final convolution -- are in sections.py.
 """
 from __future__ import annotations
 
@@ -125,8 +126,9 @@ class _SideCtx:
         torch.cuda.current_stream().wait_stream(self.stream)
 
 
-def _ptr(t: Optional[torch.Tensor]):
-    return None if t is None else c_void_p(t.data_ptr())
+def _ptr(t):
+    """launch argument of a tensor (None: a null pointer; an address computed by the caller passes through)"""
+    return t if t is None or isinstance(t, c_void_p) else c_void_p(t.data_ptr())
 
 
 def side_ctx(step, enabled: bool = True) -> Optional[_SideCtx]:

@@ -2,6 +2,9 @@
 // activation once with 16-B loads; reductions are per-thread fp32 partials -> LDS tree ->
 // per-chunk slab -> fp64 finalize (deterministic, no atomics).
 //   R = B*H*W for BatchNorm2d, R = B for BatchNorm1d (models/networks.py:16,40,66,89).
+// The building blocks every kernel below shares are stated once, up front: the row walk (walk_rows), the
+// per-thread channel constants (chan_const), the block column sum (block_colsum), the statistics finalisation (bn_finalize) and the
+// backward expressions (bn_g, bn_dx); the host side has one workspace layout (bn_ws) and one launcher per stage.
 #include <stdlib.h>
 #include "common.h"
 #include "problems.h"
@@ -55,6 +58,127 @@ __device__ __forceinline__ float act_grad_pre(float u, int act, float slope) {
     default: return 1.f;
   }
 }
+// derivative of act at the activation's own output v
+__device__ __forceinline__ float act_grad_from_y(float v, int act, float slope) {
+  switch (act) {
+    case ACT_RELU: return v > 0.f ? 1.f : 0.f;
+    case ACT_LRELU: return v > 0.f ? 1.f : slope;
+    case ACT_TANH: return 1.f - v * v;
+    case ACT_SIGMOID: return v * (1.f - v);
+    default: return 1.f;
+  }
+}
+
+// ---- the shared pieces ---------------------------------------------------------------------------------------------------------------
+// 4 consecutive floats: one 16-B access when vec, else element by element over the nv (< 4 at the last quad) that exist
+__device__ __forceinline__ vp_f32x4 ld4(const float* __restrict__ p, bool vec, int nv) {
+  if (vec) return *reinterpret_cast<const vp_f32x4*>(p);
+  vp_f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
+  return v;
+}
+__device__ __forceinline__ void ld4(float (&v)[4], const float* __restrict__ p, bool vec, int nv) {
+  const vp_f32x4 t = ld4(p, vec, nv);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v[j] = t[j];
+}
+__device__ __forceinline__ void st4(float* __restrict__ p, const vp_f32x4& v, bool vec, int nv) {
+  if (vec) { *reinterpret_cast<vp_f32x4*>(p) = v; return; }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) if (j < nv) p[j] = v[j];
+}
+
+// What one thread holds of one row: N quads (x | x, dy | branch 1, branch 2 | branch 1, branch 2, dy), as floats: kept as the
+// 16-B vectors they were loaded as, the tiled backward kernel takes 16 more VGPRs and two others lose a wave of occupancy.
+template <int N> struct Row { float v[N][4]; };
+
+// THE row walk: a thread visits rows r, r + 16, ... < r1.  U rows per trip with all of the trip's loads issued before the first use
+// (one load per trip left the small layers at 2-3 TB/s), consumed in row order, then a one-row tail: sums taken in use() see the rows
+// in the same order whatever U is.  trips = false (element-wise loads) walks row by row.
+template <int U, class Load, class Use>
+__device__ __forceinline__ void walk_rows(int r, int r1, bool trips, Load load, Use use) {
+  if (trips) {
+    for (; r + (U - 1) * BN_TY < r1; r += U * BN_TY) {
+      decltype(load(r)) v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) v[u] = load(r + u * BN_TY);
+#pragma unroll
+      for (int u = 0; u < U; ++u) use(r + u * BN_TY, v[u]);
+    }
+  }
+  for (; r < r1; r += BN_TY) use(r, load(r));
+}
+
+// Per-thread constants of a thread's 4 channels c .. c + 3, of which the first nv exist (nv <= 0: none, and then mean and rstd are
+// not touched).  A channel outside nv gives mean 0, rstd 0, gamma 1, beta 0; so does a null gamma or beta.
+struct ChanConst { float mu[4], rs[4], ga[4], be[4]; };
+__device__ __forceinline__ ChanConst chan_const(const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                const float* __restrict__ gamma, const float* __restrict__ beta, int c, int nv) {
+  ChanConst k;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool ok = j < nv;
+    k.mu[j] = ok ? mean[c + j] : 0.f;
+    k.rs[j] = ok ? rstd[c + j] : 0.f;
+    k.ga[j] = (ok && gamma) ? gamma[c + j] : 1.f;
+    k.be[j] = (ok && beta) ? beta[c + j] : 0.f;
+  }
+  return k;
+}
+
+// One more term of a pair of running sums (sum a, sum a * b): (x - pivot, its square) or (g, g * xhat).  The fma is explicit; the compiler
+// may still contract `sa += a` with the multiplication that made a (DESIGN.md section 23 on what that means for the pair blend).
+__device__ __forceinline__ void sum_pair(float& sa, float& sab, float a, float b) {
+  sa += a;
+  sab = fmaf(a, b, sab);
+}
+
+// Block column sum of N running sums: every thread (tx, ty) of the 16 x 16 map hands in s[q][0..3] for its 4 channels; thread t <
+// N * 64 gets back sum q = t / 64 of the block's channel cc = t % 64, added over the 16 row lanes in lane order (other threads: 0).
+template <int N>
+__device__ __forceinline__ float block_colsum(const float (&s)[N][4]) {
+  __shared__ float sh[N][BN_TY][BN_CH + 4];
+  const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
+#pragma unroll
+  for (int q = 0; q < N; ++q)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sh[q][ty][tx * 4 + j] = s[q][j];
+  __syncthreads();
+  float t = 0.f;
+  if (threadIdx.x < N * BN_CH) {
+    const int q = threadIdx.x / BN_CH, cc = threadIdx.x % BN_CH;
+#pragma unroll
+    for (int k = 0; k < BN_TY; ++k) t += sh[q][k][cc];
+  }
+  return t;
+}
+
+// Statistics of one channel from the fp64 sums s = sum (x - pivot), q = sum (x - pivot)^2 over R rows: mean, rstd, and the running
+// statistics (momentum-weighted, the variance unbiased) where given.
+__device__ __forceinline__ void bn_finalize(double s, double q, int R, float pivot, float eps, float momentum, float& mean, float& rstd,
+                                            float* __restrict__ rm, float* __restrict__ rv) {
+  const double ms = s / R;                 // mean of (x - pivot)
+  double var = q / R - ms * ms;
+  if (var < 0.0) var = 0.0;
+  const double m = (double)pivot + ms;
+  mean = (float)m;
+  rstd = (float)(1.0 / sqrt(var + (double)eps));
+  if (rm) *rm = (1.f - momentum) * *rm + momentum * (float)m;
+  if (rv) {
+    const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
+    *rv = (1.f - momentum) * *rv + momentum * (float)unb;
+  }
+}
+
+// g = dy * act'(gamma * xhat + beta)
+__device__ __forceinline__ float bn_g(float dy, float xh, float ga, float be, int act, float slope) {
+  return dy * act_grad_pre(fmaf(ga, xh, be), act, slope);
+}
+// dx = gamma * rstd * (g - (k0 + xhat * k1)) with k0 = sum_g / R, k1 = sum_gx / R (both 0 without batch statistics)
+__device__ __forceinline__ float bn_dx(float ga, float rs, float g, float xh, float k0, float k1) {
+  return ga * rs * (g - fmaf(xh, k1, k0));
+}
 
 // MODE 0: (sum x, sum x^2).  MODE 1: (sum g, sum g*xhat) with g = dy * act'(gamma*xhat+beta).
 template <int MODE>
@@ -62,99 +186,49 @@ __global__ void __launch_bounds__(256) bn_partial_kernel(const float* __restrict
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          float* __restrict__ part, int R, int C, int rows_per_chunk,
-                                                         int act, float slope, size_t bxs = 0, size_t bps = 0) {
+                                                         int act, float slope, size_t bxs, size_t bps) {
   // blockIdx.z = image index of a batched (InstanceNorm) call: bxs elements per image, bps partial floats per image
   x += blockIdx.z * bxs; part += blockIdx.z * bps;
   if (MODE == 1) { dy += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C; }
-  __shared__ float sh[2][BN_TY][BN_CH + 4];
   const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
   const int c = blockIdx.y * BN_CH + tx * 4;
   const int r0 = blockIdx.x * rows_per_chunk;
   const int r1 = min(R, r0 + rows_per_chunk);
-  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+  float s[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   const bool vec = (C % 4 == 0);
-  float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool ok = c + j < C;
-    mu[j] = (MODE == 1 && ok) ? mean[c + j] : 0.f;
-    rs[j] = (MODE == 1 && ok) ? rstd[c + j] : 0.f;
-    ga[j] = (MODE == 1 && ok && gamma) ? gamma[c + j] : 1.f;
-    be[j] = (MODE == 1 && ok && beta) ? beta[c + j] : 0.f;
-    // MODE 0 sums (x - pivot) and (x - pivot)^2 with pivot = the channel's value in row 0 (bn_stats_final adds it back):
-    // E[x^2] - E[x]^2 on raw values loses log2(mean^2 / var) bits, which for a Linear -> BatchNorm1d over a batch of 4
-    // similar images (mean^2 / var ~ 1e3-1e4) turned 2e-7 of input rounding into 1e-3 of sigma
-    if (MODE == 0) mu[j] = ok ? x[c + j] : 0.f;
-  }
+  const int nv = C - c;
+  // MODE 0 sums (x - pivot) and (x - pivot)^2 with pivot = the channel's value in row 0, held in mu (bn_finalize adds it back):
+  // E[x^2] - E[x]^2 on raw values loses log2(mean^2 / var) bits, which for a Linear -> BatchNorm1d over a batch of 4
+  // similar images (mean^2 / var ~ 1e3-1e4) turned 2e-7 of input rounding into 1e-3 of sigma
+  const ChanConst k = MODE == 0 ? chan_const(x, x, nullptr, nullptr, c, nv) : chan_const(mean, rstd, gamma, beta, c, nv);
   if (c < C) {
-    auto accum = [&](const float (&xv)[4], const float (&gv)[4]) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        if (MODE == 0) {
-          const float d = xv[j] - mu[j];
-          s0[j] += d;
-          s1[j] = fmaf(d, d, s1[j]);           // (explicit fma here and in bn_small_*: the two paths must round identically)
-        } else {
-          const float xh = (xv[j] - mu[j]) * rs[j];
-          const float g = gv[j] * act_grad_pre(fmaf(ga[j], xh, be[j]), act, slope);
-          s0[j] += g;
-          s1[j] = fmaf(g, xh, s1[j]);
-        }
-      }
-    };
-    int r = r0 + ty;
-    if (vec) {
-      // four rows per trip: 4 (MODE 0) or 8 (MODE 1) independent 16-B loads in flight; the sums are still taken in
-      // row order, so the result does not depend on the unrolling
-      for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {
-        vp_f32x4 tx4[4], td4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const size_t off = (size_t)(r + u * BN_TY) * C + c;
-          tx4[u] = *reinterpret_cast<const vp_f32x4*>(x + off);
-          if (MODE == 1) td4[u] = *reinterpret_cast<const vp_f32x4*>(dy + off);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          float xv[4] = {tx4[u][0], tx4[u][1], tx4[u][2], tx4[u][3]}, gv[4] = {0.f, 0.f, 0.f, 0.f};
-          if (MODE == 1) { gv[0] = td4[u][0]; gv[1] = td4[u][1]; gv[2] = td4[u][2]; gv[3] = td4[u][3]; }
-          accum(xv, gv);
-        }
-      }
-    }
-    for (; r < r1; r += BN_TY) {
-      float xv[4], gv[4] = {0.f, 0.f, 0.f, 0.f};
-      const size_t off = (size_t)r * C + c;
-      if (vec) {
-        vp_f32x4 t = *reinterpret_cast<const vp_f32x4*>(x + off);
-        xv[0] = t[0]; xv[1] = t[1]; xv[2] = t[2]; xv[3] = t[3];
-        if (MODE == 1) {
-          vp_f32x4 d = *reinterpret_cast<const vp_f32x4*>(dy + off);
-          gv[0] = d[0]; gv[1] = d[1]; gv[2] = d[2]; gv[3] = d[3];
-        }
-      } else {
+    constexpr int N = MODE == 0 ? 1 : 2;
+    // 4 (MODE 0) or 8 (MODE 1) independent 16-B loads in flight
+    walk_rows<4>(r0 + ty, r1, vec,
+      [&](int r) {
+        const size_t off = (size_t)r * C + c;
+        Row<N> v;
+        ld4(v.v[0], x + off, vec, nv);
+        if (MODE == 1) ld4(v.v[N - 1], dy + off, vec, nv);
+        return v;
+      },
+      [&](int, const Row<N>& v) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          xv[j] = (c + j < C) ? x[off + j] : 0.f;
-          if (MODE == 1) gv[j] = (c + j < C) ? dy[off + j] : 0.f;
+          if (MODE == 0) {
+            const float d = v.v[0][j] - k.mu[j];
+            sum_pair(s[0][j], s[1][j], d, d);
+          } else {
+            const float xh = (v.v[0][j] - k.mu[j]) * k.rs[j];
+            sum_pair(s[0][j], s[1][j], bn_g(v.v[N - 1][j], xh, k.ga[j], k.be[j], act, slope), xh);
+          }
         }
-      }
-      accum(xv, gv);
-    }
+      });
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    sh[0][ty][tx * 4 + j] = s0[j];
-    sh[1][ty][tx * 4 + j] = s1[j];
-  }
-  __syncthreads();
+  const float t = block_colsum<2>(s);
   if (threadIdx.x < 2 * BN_CH) {
-    const int which = threadIdx.x / BN_CH, cc = threadIdx.x % BN_CH;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < BN_TY; ++k) s += sh[which][k][cc];
-    const int cg = blockIdx.y * BN_CH + cc;
-    if (cg < C) part[((size_t)which * gridDim.x + blockIdx.x) * C + cg] = s;
+    const int which = threadIdx.x / BN_CH, cg = blockIdx.y * BN_CH + threadIdx.x % BN_CH;
+    if (cg < C) part[((size_t)which * gridDim.x + blockIdx.x) * C + cg] = t;
   }
 }
 
@@ -187,28 +261,18 @@ __device__ __forceinline__ void bn_final_reduce(const float* __restrict__ part, 
 __global__ void __launch_bounds__(256) bn_stats_final_kernel(const float* __restrict__ part, int nchunk, int R, int C, float eps,
                                                              float momentum, float* __restrict__ mean, float* __restrict__ rstd,
                                                              float* __restrict__ rm, float* __restrict__ rv, const float* __restrict__ x,
-                                                             size_t bps = 0, size_t bxs = 0) {
+                                                             size_t bps, size_t bxs) {
   part += blockIdx.z * bps; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C; x += blockIdx.z * bxs;
   const int c = blockIdx.x * FIN_C + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   double s, q;
   bn_final_reduce(part, nchunk, C, c, lane, s, q);
   if (lane != 0 || c >= C) return;
-  const double ms = s / R;                 // mean of (x - pivot), pivot = x[row 0][c] as in bn_partial_kernel<0>
-  double var = q / R - ms * ms;
-  if (var < 0.0) var = 0.0;
-  const double m = (double)x[c] + ms;
-  mean[c] = (float)m;
-  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)m;
-  if (rv) {
-    const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
-    rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
-  }
+  bn_finalize(s, q, R, x[c], eps, momentum, mean[c], rstd[c], rm ? rm + c : nullptr, rv ? rv + c : nullptr);   // pivot = x[row 0][c]
 }
 
 __global__ void __launch_bounds__(256) bn_bwd_final_kernel(const float* __restrict__ part, int nchunk, int C,
                                                            float* __restrict__ sum_g, float* __restrict__ sum_gx,
-                                                           float* __restrict__ dgamma, float* __restrict__ dbeta, size_t bps = 0) {
+                                                           float* __restrict__ dgamma, float* __restrict__ dbeta, size_t bps) {
   part += blockIdx.z * bps; sum_g += blockIdx.z * (size_t)C; sum_gx += blockIdx.z * (size_t)C;
   const int c = blockIdx.x * FIN_C + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   double s, q;
@@ -220,71 +284,35 @@ __global__ void __launch_bounds__(256) bn_bwd_final_kernel(const float* __restri
   if (dgamma) dgamma[c] = (float)q;
 }
 
+// ---- flat passes for C % 4 != 0, one element per thread and trip: no split planes (they need C % 4 == 0), so no saturation flag
 // y = act(gamma * (x - mean) * rstd + beta)
 __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                          const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                          const float* __restrict__ beta, float* __restrict__ y, size_t n,
-                                                         int C, int act, float slope, u16_t* __restrict__ y_split,
-                                                         size_t bxs = 0) {
-  x += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
-  if (y) y += blockIdx.z * bxs;
-  const bool vec = (C % 4 == 0);
-  if (vec) {
-    const size_t n4 = n / 4;
-    const int C4 = C / 4;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-      const int c = (int)(i % C4) * 4;
-      vp_f32x4 v = *reinterpret_cast<const vp_f32x4*>(x + i * 4);
-      vp_f32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        o[j] = act_apply(bn_pre(v[j], mean[c + j], rstd[c + j], gamma ? gamma[c + j] : 1.f, beta ? beta[c + j] : 0.f), act, slope);
-      }
-      if (y) *reinterpret_cast<vp_f32x4*>(y + i * 4) = o;
-      if (y_split) store_split4(y_split, n, i * 4, o[0], o[1], o[2], o[3]);
-    }
-  } else {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-      const int c = (int)(i % C);
-      y[i] = act_apply(bn_pre(x[i], mean[c], rstd[c], gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f), act, slope);
-    }
+                                                         int C, int act, float slope, size_t bxs) {
+  x += blockIdx.z * bxs; y += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    y[i] = act_apply(bn_pre(x[i], mean[c], rstd[c], gamma ? gamma[c] : 1.f, beta ? beta[c] : 0.f), act, slope);
   }
 }
 
-// dx = gamma*rstd*(g - [batch_stats]*(sum_g + xhat*sum_gx)/R)
+// dx = gamma*rstd*(g - [batch_stats]*(sum_g + xhat*sum_gx)/R): summed and scaled in this order, not bn_dx's fma of pre-scaled sums,
+// so this path and the tiled one may differ in the last bit
 __global__ void __launch_bounds__(256) bn_act_bwd_kernel(const float* __restrict__ x, const float* dy,
                                                          const float* __restrict__ mean, const float* __restrict__ rstd,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          const float* __restrict__ sum_g, const float* __restrict__ sum_gx,
                                                          float* dx, size_t n, int C, float invR, int act,
-                                                         float slope, u16_t* __restrict__ dx_split, size_t bxs = 0) {
-  x += blockIdx.z * bxs; dy += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
+                                                         float slope, size_t bxs) {
+  x += blockIdx.z * bxs; dy += blockIdx.z * bxs; dx += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
   sum_g += blockIdx.z * (size_t)C; sum_gx += blockIdx.z * (size_t)C;
-  if (dx) dx += blockIdx.z * bxs;
-  const bool vec = (C % 4 == 0);
-  const size_t cnt = vec ? n / 4 : n;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (size_t)gridDim.x * blockDim.x) {
-    if (vec) {
-      const int c = (int)(i % (C / 4)) * 4;
-      vp_f32x4 xv = *reinterpret_cast<const vp_f32x4*>(x + i * 4);
-      vp_f32x4 dv = *reinterpret_cast<const vp_f32x4*>(dy + i * 4);
-      vp_f32x4 o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float ga = gamma ? gamma[c + j] : 1.f, be = beta ? beta[c + j] : 0.f;
-        const float xh = (xv[j] - mean[c + j]) * rstd[c + j];
-        const float g = dv[j] * act_grad_pre(fmaf(ga, xh, be), act, slope);
-        o[j] = ga * rstd[c + j] * (g - (sum_g[c + j] + xh * sum_gx[c + j]) * invR);
-      }
-      if (dx) *reinterpret_cast<vp_f32x4*>(dx + i * 4) = o;
-      if (dx_split) store_split4(dx_split, n, i * 4, o[0], o[1], o[2], o[3]);
-    } else {
-      const int c = (int)(i % C);
-      const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
-      const float xh = (x[i] - mean[c]) * rstd[c];
-      const float g = dy[i] * act_grad_pre(fmaf(ga, xh, be), act, slope);
-      dx[i] = ga * rstd[c] * (g - (sum_g[c] + xh * sum_gx[c]) * invR);
-    }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    const float ga = gamma ? gamma[c] : 1.f, be = beta ? beta[c] : 0.f;
+    const float xh = (x[i] - mean[c]) * rstd[c];
+    const float g = bn_g(dy[i], xh, ga, be, act, slope);
+    dx[i] = ga * rstd[c] * (g - (sum_g[c] + xh * sum_gx[c]) * invR);
   }
 }
 
@@ -294,18 +322,8 @@ __global__ void act_fwd_kernel(const float* __restrict__ x, float* __restrict__ 
 }
 __global__ void act_bwd_from_y_kernel(const float* __restrict__ y, const float* dy, float* dx,
                                       size_t n, int act, float slope) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float v = y[i];
-    float d;
-    switch (act) {
-      case ACT_RELU: d = v > 0.f ? 1.f : 0.f; break;
-      case ACT_LRELU: d = v > 0.f ? 1.f : slope; break;
-      case ACT_TANH: d = 1.f - v * v; break;
-      case ACT_SIGMOID: d = v * (1.f - v); break;
-      default: d = 1.f;
-    }
-    dx[i] = dy[i] * d;
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    dx[i] = dy[i] * act_grad_from_y(y[i], act, slope);
 }
 
 // ---- fast paths for C % 4 == 0: same (16 float4 columns x 16 rows) thread map as bn_partial_kernel, so the
@@ -315,49 +333,28 @@ __global__ void __launch_bounds__(256) bn_act_fwd_tiled_kernel(const float* __re
                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ y,
                                                                u16_t* __restrict__ y_split, int R, int C, int rows_per_chunk,
-                                                               int act, float slope, size_t bxs = 0, int sfmt = SPLIT_BF16) {
+                                                               int act, float slope, size_t bxs, int sfmt) {
   x += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
   if (y) y += blockIdx.z * bxs;
   const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
   const int c = blockIdx.y * BN_CH + tx * 4;
   if (c >= C) return;
-  float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    mu[j] = mean[c + j]; rs[j] = rstd[c + j];
-    ga[j] = gamma ? gamma[c + j] : 1.f; be[j] = beta ? beta[c + j] : 0.f;
-  }
+  const ChanConst k = chan_const(mean, rstd, gamma, beta, c, 4);
   const int r0 = blockIdx.x * rows_per_chunk;
   const int r1 = min(R, r0 + rows_per_chunk);
   // split planes span all images of a batched (InstanceNorm) launch: plane = gridDim.z * R * C elements, image z at z * bxs
   const size_t n = (size_t)R * C * gridDim.z;
   if (y_split) y_split += blockIdx.z * bxs;
-  // four rows per trip: four independent 16-B loads in flight before the first use (one load per trip left the
-  // small layers at 2-3 TB/s)
-  int r = r0 + ty;
-  for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {
-    vp_f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const vp_f32x4*>(x + (size_t)(r + u * BN_TY) * C + c);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t off = (size_t)(r + u * BN_TY) * C + c;
+  walk_rows<4>(r0 + ty, r1, true,                       // four independent 16-B loads in flight
+    [&](int r) { Row<1> v; ld4(v.v[0], x + (size_t)r * C + c, true, 4); return v; },
+    [&](int r, const Row<1>& v) {
+      const size_t off = (size_t)r * C + c;
       vp_f32x4 o;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = act_apply(bn_pre(v[u][j], mu[j], rs[j], ga[j], be[j]), act, slope);
+      for (int j = 0; j < 4; ++j) o[j] = act_apply(bn_pre(v.v[0][j], k.mu[j], k.rs[j], k.ga[j], k.be[j]), act, slope);
       if (y) *reinterpret_cast<vp_f32x4*>(y + off) = o;
       if (y_split) store_split4(y_split, n, off, o[0], o[1], o[2], o[3], sfmt);
-    }
-  }
-  for (; r < r1; r += BN_TY) {
-    const size_t off = (size_t)r * C + c;
-    const vp_f32x4 v = *reinterpret_cast<const vp_f32x4*>(x + off);
-    vp_f32x4 o;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) o[j] = act_apply(bn_pre(v[j], mu[j], rs[j], ga[j], be[j]), act, slope);
-    if (y) *reinterpret_cast<vp_f32x4*>(y + off) = o;
-    if (y_split) store_split4(y_split, n, off, o[0], o[1], o[2], o[3], sfmt);
-  }
+    });
 }
 
 __global__ void __launch_bounds__(256) bn_act_bwd_tiled_kernel(const float* __restrict__ x, const float* dy,
@@ -366,55 +363,43 @@ __global__ void __launch_bounds__(256) bn_act_bwd_tiled_kernel(const float* __re
                                                                const float* __restrict__ sum_g, const float* __restrict__ sum_gx,
                                                                float* dx, u16_t* __restrict__ dx_split, int R, int C,
                                                                int rows_per_chunk, float invR, int act, float slope,
-                                                               size_t bxs = 0, int sfmt = SPLIT_BF16, float sscale = 1.f,
-                                                               int* __restrict__ sat = nullptr) {
+                                                               size_t bxs, int sfmt, float sscale, int* __restrict__ sat) {
   x += blockIdx.z * bxs; dy += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
   sum_g += blockIdx.z * (size_t)C; sum_gx += blockIdx.z * (size_t)C;
   if (dx) dx += blockIdx.z * bxs;
   const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
   const int c = blockIdx.y * BN_CH + tx * 4;
   if (c >= C) return;
-  float mu[4], rs[4], ga[4], be[4], k0[4], k1[4];
+  const ChanConst k = chan_const(mean, rstd, gamma, beta, c, 4);
+  float k0[4], k1[4];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    mu[j] = mean[c + j]; rs[j] = rstd[c + j];
-    ga[j] = gamma ? gamma[c + j] : 1.f; be[j] = beta ? beta[c + j] : 0.f;
-    k0[j] = sum_g[c + j] * invR; k1[j] = sum_gx[c + j] * invR;
-  }
+  for (int j = 0; j < 4; ++j) { k0[j] = sum_g[c + j] * invR; k1[j] = sum_gx[c + j] * invR; }
   const int r0 = blockIdx.x * rows_per_chunk;
   const int r1 = min(R, r0 + rows_per_chunk);
   const size_t n = (size_t)R * C * gridDim.z;          // (batched launch: see bn_act_fwd_tiled_kernel)
   if (dx_split) dx_split += blockIdx.z * bxs;
-  auto emit = [&](size_t off, const vp_f32x4& xv, const vp_f32x4& dv) {
-    vp_f32x4 o;
+  walk_rows<4>(r0 + ty, r1, true,                       // eight independent 16-B loads in flight
+    [&](int r) {
+      const size_t off = (size_t)r * C + c;
+      Row<2> v;
+      ld4(v.v[0], x + off, true, 4);
+      ld4(v.v[1], dy + off, true, 4);
+      return v;
+    },
+    [&](int r, const Row<2>& v) {
+      const size_t off = (size_t)r * C + c;
+      vp_f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float xh = (xv[j] - mu[j]) * rs[j];
-      const float g = dv[j] * act_grad_pre(fmaf(ga[j], xh, be[j]), act, slope);
-      o[j] = ga[j] * rs[j] * (g - fmaf(xh, k1[j], k0[j]));       // (explicit fma: bn_small_bwd_kernel must round identically)
-    }
-    if (dx) *reinterpret_cast<vp_f32x4*>(dx + off) = o;
-    if (dx_split) store_split4(dx_split, n, off, o[0] * sscale, o[1] * sscale, o[2] * sscale, o[3] * sscale, sfmt);
-    // fp16 pairs clamp at +-65504 (split.h): tell the caller that a scaled gradient left fp16's range (a sticky flag, any writer wins)
-    if (sat && sfmt == SPLIT_F16 &&
-        fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))) * sscale > 65504.f) *sat = 1;
-  };
-  int r = r0 + ty;
-  for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {          // eight independent 16-B loads in flight
-    vp_f32x4 xv[4], dv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t off = (size_t)(r + u * BN_TY) * C + c;
-      xv[u] = *reinterpret_cast<const vp_f32x4*>(x + off);
-      dv[u] = *reinterpret_cast<const vp_f32x4*>(dy + off);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) emit((size_t)(r + u * BN_TY) * C + c, xv[u], dv[u]);
-  }
-  for (; r < r1; r += BN_TY) {
-    const size_t off = (size_t)r * C + c;
-    emit(off, *reinterpret_cast<const vp_f32x4*>(x + off), *reinterpret_cast<const vp_f32x4*>(dy + off));
-  }
+      for (int j = 0; j < 4; ++j) {
+        const float xh = (v.v[0][j] - k.mu[j]) * k.rs[j];
+        o[j] = bn_dx(k.ga[j], k.rs[j], bn_g(v.v[1][j], xh, k.ga[j], k.be[j], act, slope), xh, k0[j], k1[j]);
+      }
+      if (dx) *reinterpret_cast<vp_f32x4*>(dx + off) = o;
+      if (dx_split) store_split4(dx_split, n, off, o[0] * sscale, o[1] * sscale, o[2] * sscale, o[3] * sscale, sfmt);
+      // fp16 pairs clamp at +-65504 (split.h): tell the caller that a scaled gradient left fp16's range (a sticky flag, any writer wins)
+      if (sat && sfmt == SPLIT_F16 &&
+          fmaxf(fmaxf(fabsf(o[0]), fabsf(o[1])), fmaxf(fabsf(o[2]), fabsf(o[3]))) * sscale > 65504.f) *sat = 1;
+    });
 }
 
 // elementwise passes want more, smaller chunks than the reductions (no partial slabs to combine)
@@ -437,76 +422,56 @@ inline BnGrid bn_apply_grid(int R, int C) {
 // ---- BatchNorm over a handful of rows (the dense layers: R = batch <= 64) in ONE launch --------------------------------------------
 // nn.BatchNorm1d + F.relu behind nn.Linear (models/networks.py:66-67,89-90) normalises over the batch only: the three-launch form
 // (partial sums, finaliser, apply) is pure launch latency there (3 x ~6 us for 32 rows).  One workgroup owns 64 channels and all
-// rows; a thread keeps its <= 4 rows of 4 channels in registers.  The arithmetic is the three-launch path's, step for step (pivoted
-// fp32 sums in the same order, fp64 finalisation, bn_pre for the normalised value), so results are bit-identical to it.
+// rows; a thread keeps its <= 4 rows of 4 channels in registers.  The arithmetic is the three-launch path's, step for step, through
+// the same functions (sum_pair in the same order, block_colsum, bn_finalize, bn_pre, bn_g, bn_dx), so results are bit-identical to it.
 constexpr int BN_SMALL_R = 4 * BN_TY;       // 64 rows
 
 __global__ void __launch_bounds__(256) bn_small_fwd_kernel(const float* __restrict__ x, int R, int C, float eps, float momentum,
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            float* __restrict__ mean, float* __restrict__ rstd, float* __restrict__ rm,
                                                            float* __restrict__ rv, float* __restrict__ y, int act, float slope) {
-  __shared__ float sh[2][BN_TY][BN_CH + 4];
   __shared__ float fin[2][BN_CH];
   const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
   const int c = blockIdx.x * BN_CH + tx * 4;
   const bool cok = c < C;                     // C % 4 == 0: a quad is inside or outside
-  vp_f32x4 xv[4], pv = {0.f, 0.f, 0.f, 0.f};
-  if (cok) pv = *reinterpret_cast<const vp_f32x4*>(x + c);           // pivot = row 0
-  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+  float xv[4][4];
+  const ChanConst pv = chan_const(x, x, nullptr, nullptr, c, cok ? 4 : 0);                 // mu = pivot = row 0
+  float s[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int r = ty + BN_TY * k;
+  for (int i = 0; i < 4; ++i) {
+    const int r = ty + BN_TY * i;
     if (cok && r < R) {
-      xv[k] = *reinterpret_cast<const vp_f32x4*>(x + (size_t)r * C + c);
+      ld4(xv[i], x + (size_t)r * C + c, true, 4);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { const float d = xv[k][j] - pv[j]; s0[j] += d; s1[j] = fmaf(d, d, s1[j]); }
+      for (int j = 0; j < 4; ++j) { const float d = xv[i][j] - pv.mu[j]; sum_pair(s[0][j], s[1][j], d, d); }
     }
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sh[0][ty][tx * 4 + j] = s0[j]; sh[1][ty][tx * 4 + j] = s1[j]; }
-  __syncthreads();
-  if (threadIdx.x < 2 * BN_CH) {
-    const int which = threadIdx.x / BN_CH, cc = threadIdx.x % BN_CH;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < BN_TY; ++k) s += sh[which][k][cc];
-    fin[which][cc] = s;
-  }
+  const float t = block_colsum<2>(s);
+  if (threadIdx.x < 2 * BN_CH) fin[threadIdx.x / BN_CH][threadIdx.x % BN_CH] = t;
   __syncthreads();
   if (threadIdx.x < BN_CH) {
     const int cc = threadIdx.x, cg = blockIdx.x * BN_CH + cc;
     if (cg < C) {
-      const double ms = (double)fin[0][cc] / R;
-      double var = (double)fin[1][cc] / R - ms * ms;
-      if (var < 0.0) var = 0.0;
-      const double m = (double)x[cg] + ms;
-      const float mf = (float)m, rf = (float)(1.0 / sqrt(var + (double)eps));
+      float mf, rf;
+      bn_finalize((double)fin[0][cc], (double)fin[1][cc], R, x[cg], eps, momentum, mf, rf, rm ? rm + cg : nullptr, rv ? rv + cg : nullptr);
       mean[cg] = mf;
       rstd[cg] = rf;
-      if (rm) rm[cg] = (1.f - momentum) * rm[cg] + momentum * mf;
-      if (rv) {
-        const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
-        rv[cg] = (1.f - momentum) * rv[cg] + momentum * (float)unb;
-      }
       fin[0][cc] = mf;
       fin[1][cc] = rf;
     }
   }
   __syncthreads();
   if (!cok || !y) return;
-  float mu[4], rs[4], ga[4], be[4];
+  ChanConst k = chan_const(mean, rstd, gamma, beta, c, 4);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    mu[j] = fin[0][tx * 4 + j]; rs[j] = fin[1][tx * 4 + j];
-    ga[j] = gamma ? gamma[c + j] : 1.f; be[j] = beta ? beta[c + j] : 0.f;
-  }
+  for (int j = 0; j < 4; ++j) { k.mu[j] = fin[0][tx * 4 + j]; k.rs[j] = fin[1][tx * 4 + j]; }     // as this block finalised them, from LDS
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int r = ty + BN_TY * k;
+  for (int i = 0; i < 4; ++i) {
+    const int r = ty + BN_TY * i;
     if (r < R) {
       vp_f32x4 o;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) o[j] = act_apply(bn_pre(xv[k][j], mu[j], rs[j], ga[j], be[j]), act, slope);
+      for (int j = 0; j < 4; ++j) o[j] = act_apply(bn_pre(xv[i][j], k.mu[j], k.rs[j], k.ga[j], k.be[j]), act, slope);
       *reinterpret_cast<vp_f32x4*>(y + (size_t)r * C + c) = o;
     }
   }
@@ -517,69 +482,51 @@ __global__ void __launch_bounds__(256) bn_small_bwd_kernel(const float* __restri
                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
                                                            float* __restrict__ dx, float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                            int R, int C, float invR, int act, float slope) {
-  __shared__ float sh[2][BN_TY][BN_CH + 4];
   __shared__ float fin[2][BN_CH];
   const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
   const int c = blockIdx.x * BN_CH + tx * 4;
   const bool cok = c < C;
-  float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    mu[j] = cok ? mean[c + j] : 0.f; rs[j] = cok ? rstd[c + j] : 0.f;
-    ga[j] = (cok && gamma) ? gamma[c + j] : 1.f; be[j] = (cok && beta) ? beta[c + j] : 0.f;
-  }
+  const ChanConst k = chan_const(mean, rstd, gamma, beta, c, cok ? 4 : 0);
   float gq[4][4], xh[4][4];
-  float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+  float s[2][4] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int r = ty + BN_TY * k;
+  for (int i = 0; i < 4; ++i) {
+    const int r = ty + BN_TY * i;
     if (cok && r < R) {
-      const vp_f32x4 xv = *reinterpret_cast<const vp_f32x4*>(x + (size_t)r * C + c);
-      const vp_f32x4 dv = *reinterpret_cast<const vp_f32x4*>(dy + (size_t)r * C + c);
+      float xv[4], dv[4];
+      ld4(xv, x + (size_t)r * C + c, true, 4);
+      ld4(dv, dy + (size_t)r * C + c, true, 4);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        xh[k][j] = (xv[j] - mu[j]) * rs[j];
-        gq[k][j] = dv[j] * act_grad_pre(fmaf(ga[j], xh[k][j], be[j]), act, slope);
-        s0[j] += gq[k][j];
-        s1[j] = fmaf(gq[k][j], xh[k][j], s1[j]);
+        xh[i][j] = (xv[j] - k.mu[j]) * k.rs[j];
+        gq[i][j] = bn_g(dv[j], xh[i][j], k.ga[j], k.be[j], act, slope);
+        sum_pair(s[0][j], s[1][j], gq[i][j], xh[i][j]);
       }
     }
   }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { sh[0][ty][tx * 4 + j] = s0[j]; sh[1][ty][tx * 4 + j] = s1[j]; }
-  __syncthreads();
+  const float t = block_colsum<2>(s);
   if (threadIdx.x < 2 * BN_CH) {
     const int which = threadIdx.x / BN_CH, cc = threadIdx.x % BN_CH;
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < BN_TY; ++k) s += sh[which][k][cc];
-    fin[which][cc] = s;
+    fin[which][cc] = t;
     const int cg = blockIdx.x * BN_CH + cc;
     if (cg < C) {
-      if (which == 0 && dbeta) dbeta[cg] = s;
-      if (which == 1 && dgamma) dgamma[cg] = s;
+      if (which == 0 && dbeta) dbeta[cg] = t;
+      if (which == 1 && dgamma) dgamma[cg] = t;
     }
   }
   __syncthreads();
   if (!cok) return;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int r = ty + BN_TY * k;
+  for (int i = 0; i < 4; ++i) {
+    const int r = ty + BN_TY * i;
     if (r < R) {
       vp_f32x4 o;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float k0 = fin[0][tx * 4 + j] * invR, k1 = fin[1][tx * 4 + j] * invR;
-        o[j] = ga[j] * rs[j] * (gq[k][j] - fmaf(xh[k][j], k1, k0));
-      }
+      for (int j = 0; j < 4; ++j)
+        o[j] = bn_dx(k.ga[j], k.rs[j], gq[i][j], xh[i][j], fin[0][tx * 4 + j] * invR, fin[1][tx * 4 + j] * invR);
       *reinterpret_cast<vp_f32x4*>(dx + (size_t)r * C + c) = o;
     }
   }
-}
-
-inline size_t bn_ws_floats(int R, int C) {
-  BnGrid g = bn_grid(R, C);
-  return (size_t)2 * g.chunks_r * C + (size_t)2 * C;   // partial slabs + (sum_g, sum_gx)
 }
 
 // ---- label-gated pair of convolutions (models/network_Style_GAN.py:72-79) -----------------------------------------------------------
@@ -587,33 +534,8 @@ inline size_t bn_ws_floats(int R, int C) {
 // [0, C) are branch 1, [C, 2C) branch 2.  y[b][r][c] = w1 * act(pre(u[b][r][c])) + w2 * act(pre(u[b][r][C + c])) with w2 = label[b],
 // w1 = 1 - label[b] and pre = InstanceNorm (norm = 1: the statistics are the InstanceNorm kernels above run over 2C channels) or the
 // identity (norm = 0).  Same (16 float4 columns x 16 rows) thread map as the tiled kernels above, over the C output channels; VEC =
-// (C % 4 == 0) takes 16-B loads and stores, the other instantiation guards every element.
-template <bool VEC>
-__device__ __forceinline__ vp_f32x4 pair_ld4(const float* __restrict__ p, int nv) {
-  if (VEC) return *reinterpret_cast<const vp_f32x4*>(p);
-  vp_f32x4 v;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) v[j] = j < nv ? p[j] : 0.f;
-  return v;
-}
-template <bool VEC>
-__device__ __forceinline__ void pair_st4(float* __restrict__ p, const vp_f32x4& v, int nv) {
-  if (VEC) { *reinterpret_cast<vp_f32x4*>(p) = v; return; }
-#pragma unroll
-  for (int j = 0; j < 4; ++j) if (j < nv) p[j] = v[j];
-}
-// per-thread constants of one branch: mean / rstd of its 4 channels (identity when norm = 0)
-struct PairStat { float mu[4], rs[4]; };
-__device__ __forceinline__ PairStat pair_stat(const float* __restrict__ mean, const float* __restrict__ rstd, int c, int nv, int norm) {
-  PairStat s;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool ok = norm && j < nv;
-    s.mu[j] = ok ? mean[c + j] : 0.f;
-    s.rs[j] = ok ? rstd[c + j] : 1.f;
-  }
-  return s;
-}
+// (C % 4 == 0) takes 16-B loads and stores, the other instantiation guards every element.  A branch's per-thread constants are a
+// ChanConst of its mean and rstd (gamma 1, beta 0; nothing is loaded when norm = 0, where they are not used).
 // pre-activation value, as the forward computes it (the backward rebuilds the activation mask from the same expression)
 __device__ __forceinline__ float pair_pre(float v, float mu, float rs, int norm) { return norm ? bn_pre(v, mu, rs, 1.f, 0.f) : v; }
 // g = w * dy * act'(pre): one expression for the partial sums and the apply pass
@@ -632,40 +554,33 @@ __global__ void __launch_bounds__(256) pair_blend_fwd_kernel(const float* __rest
   if (c >= C) return;
   const int nv = min(4, C - c);
   const float w2 = label[b], w1 = 1.f - w2;
-  const PairStat s1 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, c, nv, norm);
-  const PairStat s2 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, C + c, nv, norm);
+  mean += (size_t)b * C2; rstd += (size_t)b * C2;
+  const ChanConst s1 = chan_const(mean, rstd, nullptr, nullptr, c, norm ? nv : 0);
+  const ChanConst s2 = chan_const(mean, rstd, nullptr, nullptr, C + c, norm ? nv : 0);
   const size_t n = bys * gridDim.z;                   // one split plane spans all images
   if (y_split) y_split += (size_t)b * bys;
   const int r0 = blockIdx.x * rows_per_chunk;
   const int r1 = min(R, r0 + rows_per_chunk);
-  auto emit = [&](int r, const vp_f32x4& va, const vp_f32x4& vb) {
-    vp_f32x4 o;
+  walk_rows<4>(r0 + ty, r1, true,                     // eight independent loads in flight
+    [&](int r) {
+      const float* p = u + (size_t)r * C2 + c;
+      Row<2> v;
+      ld4(v.v[0], p, VEC, nv);
+      ld4(v.v[1], p + C, VEC, nv);
+      return v;
+    },
+    [&](int r, const Row<2>& v) {
+      vp_f32x4 o;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a1 = act_apply(pair_pre(va[j], s1.mu[j], s1.rs[j], norm), act, slope);
-      const float a2 = act_apply(pair_pre(vb[j], s2.mu[j], s2.rs[j], norm), act, slope);
-      o[j] = fmaf(w2, a2, w1 * a1);
-    }
-    const size_t off = (size_t)r * C + c;
-    pair_st4<VEC>(y + off, o, nv);
-    if (VEC && y_split) store_split4(y_split, n, off, o[0], o[1], o[2], o[3]);
-  };
-  int r = r0 + ty;
-  for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {        // eight independent loads in flight
-    vp_f32x4 va[4], vb[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float* p = u + (size_t)(r + k * BN_TY) * C2 + c;
-      va[k] = pair_ld4<VEC>(p, nv);
-      vb[k] = pair_ld4<VEC>(p + C, nv);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) emit(r + k * BN_TY, va[k], vb[k]);
-  }
-  for (; r < r1; r += BN_TY) {
-    const float* p = u + (size_t)r * C2 + c;
-    emit(r, pair_ld4<VEC>(p, nv), pair_ld4<VEC>(p + C, nv));
-  }
+      for (int j = 0; j < 4; ++j) {
+        const float a1 = act_apply(pair_pre(v.v[0][j], s1.mu[j], s1.rs[j], norm), act, slope);
+        const float a2 = act_apply(pair_pre(v.v[1][j], s2.mu[j], s2.rs[j], norm), act, slope);
+        o[j] = fmaf(w2, a2, w1 * a1);
+      }
+      const size_t off = (size_t)r * C + c;
+      st4(y + off, o, VEC, nv);
+      if (VEC && y_split) store_split4(y_split, n, off, o[0], o[1], o[2], o[3]);
+    });
 }
 
 // (sum g1, sum g1 * xhat1, sum g2, sum g2 * xhat2) per (image, channel, row chunk) in one read of u and dy, written into the slab
@@ -675,7 +590,6 @@ __global__ void __launch_bounds__(256) pair_blend_partial_kernel(const float* __
                                                                  const float* __restrict__ label, const float* __restrict__ mean,
                                                                  const float* __restrict__ rstd, float* __restrict__ part, int R, int C,
                                                                  int rows_per_chunk, int act, float slope, size_t bps) {
-  __shared__ float sh[4][BN_TY][BN_CH + 4];
   const int b = blockIdx.z, C2 = 2 * C;
   const size_t bys = (size_t)R * C;
   u += (size_t)b * 2 * bys; dy += (size_t)b * bys; part += (size_t)b * bps;
@@ -689,8 +603,11 @@ __global__ void __launch_bounds__(256) pair_blend_partial_kernel(const float* __
     for (int j = 0; j < 4; ++j) s[q][j] = 0.f;
   if (c < C) {
     const float w2 = label[b], w1 = 1.f - w2;
-    const PairStat s1 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, c, nv, 1);
-    const PairStat s2 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, C + c, nv, 1);
+    mean += (size_t)b * C2; rstd += (size_t)b * C2;
+    const ChanConst s1 = chan_const(mean, rstd, nullptr, nullptr, c, nv);
+    const ChanConst s2 = chan_const(mean, rstd, nullptr, nullptr, C + c, nv);
+    const int r0 = blockIdx.x * rows_per_chunk;
+    const int r1 = min(R, r0 + rows_per_chunk);
     auto accum = [&](const vp_f32x4& va, const vp_f32x4& vb, const vp_f32x4& d) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
@@ -703,37 +620,28 @@ __global__ void __launch_bounds__(256) pair_blend_partial_kernel(const float* __
         s[3][j] = fmaf(g2, x2, s[3][j]);
       }
     };
-    const int r0 = blockIdx.x * rows_per_chunk;
-    const int r1 = min(R, r0 + rows_per_chunk);
+    // NOT walk_rows: the compiler contracts `s += g` into an fma, or not, depending on the form of this loop (vector or scalar rows,
+    // trip or tail), so any restatement moves last bits of the sums for the activations with a rounded derivative
     int r = r0 + ty;
-    // four rows per trip, summed in row order: the result does not depend on the unrolling
     for (; r + 3 * BN_TY < r1; r += 4 * BN_TY) {
       vp_f32x4 va[4], vb[4], vd[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const float* p = u + (size_t)(r + k * BN_TY) * C2 + c;
-        va[k] = pair_ld4<VEC>(p, nv);
-        vb[k] = pair_ld4<VEC>(p + C, nv);
-        vd[k] = pair_ld4<VEC>(dy + (size_t)(r + k * BN_TY) * C + c, nv);
+        va[k] = ld4(p, VEC, nv);
+        vb[k] = ld4(p + C, VEC, nv);
+        vd[k] = ld4(dy + (size_t)(r + k * BN_TY) * C + c, VEC, nv);
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) accum(va[k], vb[k], vd[k]);
     }
     for (; r < r1; r += BN_TY) {
       const float* p = u + (size_t)r * C2 + c;
-      accum(pair_ld4<VEC>(p, nv), pair_ld4<VEC>(p + C, nv), pair_ld4<VEC>(dy + (size_t)r * C + c, nv));
+      accum(ld4(p, VEC, nv), ld4(p + C, VEC, nv), ld4(dy + (size_t)r * C + c, VEC, nv));
     }
   }
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) sh[q][ty][tx * 4 + j] = s[q][j];
-  __syncthreads();
-  const int q = threadIdx.x / BN_CH, cc = threadIdx.x % BN_CH;        // 4 sums x 64 channels = 256 threads
-  float t = 0.f;
-#pragma unroll
-  for (int k = 0; k < BN_TY; ++k) t += sh[q][k][cc];
-  const int cg = blockIdx.y * BN_CH + cc;
+  const float t = block_colsum<4>(s);                                  // 4 sums x 64 channels = 256 threads
+  const int q = threadIdx.x / BN_CH, cg = blockIdx.y * BN_CH + threadIdx.x % BN_CH;
   // q & 1: 0 = sum g, 1 = sum g * xhat (the two slabs of bn_partial_kernel); q >> 1: branch, at channel offset C
   if (cg < C) part[((size_t)(q & 1) * gridDim.x + blockIdx.x) * C2 + (q >> 1) * C + cg] = t;
 }
@@ -754,8 +662,9 @@ __global__ void __launch_bounds__(256) pair_blend_bwd_kernel(const float* __rest
   if (c >= C) return;
   const int nv = min(4, C - c);
   const float w2 = label[b], w1 = 1.f - w2;
-  const PairStat s1 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, c, nv, norm);
-  const PairStat s2 = pair_stat(mean + (size_t)b * C2, rstd + (size_t)b * C2, C + c, nv, norm);
+  mean += (size_t)b * C2; rstd += (size_t)b * C2;
+  const ChanConst s1 = chan_const(mean, rstd, nullptr, nullptr, c, norm ? nv : 0);
+  const ChanConst s2 = chan_const(mean, rstd, nullptr, nullptr, C + c, norm ? nv : 0);
   float k0[2][4], k1[2][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -768,48 +677,133 @@ __global__ void __launch_bounds__(256) pair_blend_bwd_kernel(const float* __rest
   if (du_split) du_split += (size_t)b * 2 * bys;
   // bn=None without an activation (conv1, conv2 of the generator): du_j = w_j * dy, u is not read
   const bool need_u = norm || act != ACT_NONE;
-  const vp_f32x4 zero = {0.f, 0.f, 0.f, 0.f};
   const int r0 = blockIdx.x * rows_per_chunk;
   const int r1 = min(R, r0 + rows_per_chunk);
-  auto emit = [&](int r, const vp_f32x4& va, const vp_f32x4& vb, const vp_f32x4& d) {
-    vp_f32x4 oa, ob;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float g1 = pair_g(w1, d[j], pair_pre(va[j], s1.mu[j], s1.rs[j], norm), act, slope);
-      const float g2 = pair_g(w2, d[j], pair_pre(vb[j], s2.mu[j], s2.rs[j], norm), act, slope);
-      if (norm) {
-        const float x1 = (va[j] - s1.mu[j]) * s1.rs[j], x2 = (vb[j] - s2.mu[j]) * s2.rs[j];
-        oa[j] = s1.rs[j] * (g1 - fmaf(x1, k1[0][j], k0[0][j]));
-        ob[j] = s2.rs[j] * (g2 - fmaf(x2, k1[1][j], k0[1][j]));
-      } else {
-        oa[j] = g1;
-        ob[j] = g2;
+  walk_rows<2>(r0 + ty, r1, true,                       // six independent loads in flight
+    [&](int r) {
+      const float* p = u + (size_t)r * C2 + c;
+      Row<3> v = {};
+      if (need_u) {
+        ld4(v.v[0], p, VEC, nv);
+        ld4(v.v[1], p + C, VEC, nv);
       }
-    }
-    const size_t off = (size_t)r * C2 + c;
-    pair_st4<VEC>(du + off, oa, nv);
-    pair_st4<VEC>(du + off + C, ob, nv);
-    if (VEC && du_split) {
-      store_split4(du_split, n, off, oa[0], oa[1], oa[2], oa[3]);
-      store_split4(du_split, n, off + C, ob[0], ob[1], ob[2], ob[3]);
-    }
-  };
-  int r = r0 + ty;
-  for (; r + BN_TY < r1; r += 2 * BN_TY) {              // six independent loads in flight
-    vp_f32x4 va[2], vb[2], vd[2];
+      ld4(v.v[2], dy + (size_t)r * C + c, VEC, nv);
+      return v;
+    },
+    [&](int r, const Row<3>& v) {
+      vp_f32x4 oa, ob;
 #pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const float* p = u + (size_t)(r + k * BN_TY) * C2 + c;
-      va[k] = need_u ? pair_ld4<VEC>(p, nv) : zero;
-      vb[k] = need_u ? pair_ld4<VEC>(p + C, nv) : zero;
-      vd[k] = pair_ld4<VEC>(dy + (size_t)(r + k * BN_TY) * C + c, nv);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) emit(r + k * BN_TY, va[k], vb[k], vd[k]);
+      for (int j = 0; j < 4; ++j) {
+        const float g1 = pair_g(w1, v.v[2][j], pair_pre(v.v[0][j], s1.mu[j], s1.rs[j], norm), act, slope);
+        const float g2 = pair_g(w2, v.v[2][j], pair_pre(v.v[1][j], s2.mu[j], s2.rs[j], norm), act, slope);
+        if (norm) {
+          const float x1 = (v.v[0][j] - s1.mu[j]) * s1.rs[j], x2 = (v.v[1][j] - s2.mu[j]) * s2.rs[j];
+          oa[j] = bn_dx(s1.ga[j], s1.rs[j], g1, x1, k0[0][j], k1[0][j]);
+          ob[j] = bn_dx(s2.ga[j], s2.rs[j], g2, x2, k0[1][j], k1[1][j]);
+        } else {
+          oa[j] = g1;
+          ob[j] = g2;
+        }
+      }
+      const size_t off = (size_t)r * C2 + c;
+      st4(du + off, oa, VEC, nv);
+      st4(du + off + C, ob, VEC, nv);
+      if (VEC && du_split) {
+        store_split4(du_split, n, off, oa[0], oa[1], oa[2], oa[3]);
+        store_split4(du_split, n, off + C, ob[0], ob[1], ob[2], ob[3]);
+      }
+    });
+}
+
+// ---- host side: one workspace layout, one launcher per stage --------------------------------------------------------------------------
+// Workspace of a B-image call over [R][C], in floats: the partial slabs part [B][2][chunks_r][C] at 0, then sum_g [B][C], sum_gx [B][C]
+struct BnWs {
+  BnGrid g;                         // the reduction grid the slabs are laid out for
+  size_t bps;                       // partial floats per image
+  size_t sum_g, sum_gx, floats;     // offsets of the two sums, and the size of it all
+};
+inline BnWs bn_ws(int B, int R, int C) {
+  BnWs w;
+  w.g = bn_grid(R, C);
+  w.bps = (size_t)2 * w.g.chunks_r * C;
+  w.sum_g = (size_t)B * w.bps;
+  w.sum_gx = w.sum_g + (size_t)B * C;
+  w.floats = w.sum_gx + (size_t)B * C;
+  return w;
+}
+inline size_t bn_ws_bytes(int B, int R, int C) { return bn_ws(B, R, C).floats * sizeof(float); }
+
+// check_launch for stage "partial" | "final" of the entry point `name`
+static int check_stage(const char* name, const char* stage) {
+  char what[96];
+  snprintf(what, sizeof what, "%s(%s)", name, stage);
+  return check_launch(what);
+}
+
+// All launchers: B images of [R][C] (B = 1: BatchNorm), `name` = the entry point, for error messages.
+// Statistics: bn_partial_kernel<0> into the slabs, bn_stats_final_kernel into mean / rstd [B][C] (and the running statistics).
+static int launch_stats(const char* name, const float* x, int B, int R, int C, float eps, float momentum, float* mean, float* rstd,
+                        float* rm, float* rv, void* ws, hipStream_t s) {
+  const BnWs w = bn_ws(B, R, C);
+  const size_t bxs = (size_t)R * C;
+  float* part = (float*)ws;
+  hipLaunchKernelGGL((bn_partial_kernel<0>), dim3(w.g.chunks_r, w.g.chunks_c, B), dim3(256), 0, s, x, (const float*)nullptr,
+                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, R, C,
+                     w.g.rows_per_chunk, 0, 0.f, bxs, w.bps);
+  int rc = check_stage(name, "partial");
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, w.g.chunks_r, R, C,
+                     eps, momentum, mean, rstd, rm, rv, x, w.bps, bxs);
+  return check_stage(name, "final");
+}
+
+// Backward sums: partial(grid, part, bps) launches the kernel that fills the slabs over C channels, bn_bwd_final_kernel turns them into
+// sum_g / sum_gx [B][C] inside the workspace (and dgamma / dbeta where given).
+template <class Partial>
+static int launch_bwd_sums(const char* name, int B, int R, int C, float* dgamma, float* dbeta, void* ws, hipStream_t s, Partial partial) {
+  const BnWs w = bn_ws(B, R, C);
+  float* part = (float*)ws;
+  partial(w.g, part, w.bps);
+  int rc = check_stage(name, "partial");
+  if (rc) return rc;
+  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, w.g.chunks_r, C,
+                     part + w.sum_g, part + w.sum_gx, dgamma, dbeta, w.bps);
+  return check_stage(name, "final");
+}
+static int launch_bn_bwd_sums(const char* name, const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
+                              const float* beta, float* dgamma, float* dbeta, int B, int R, int C, int act, float slope, void* ws,
+                              hipStream_t s) {
+  return launch_bwd_sums(name, B, R, C, dgamma, dbeta, ws, s, [&](const BnGrid& g, float* part, size_t bps) {
+    hipLaunchKernelGGL((bn_partial_kernel<1>), dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, x, dy, mean, rstd, gamma, beta, part, R, C,
+                       g.rows_per_chunk, act, slope, (size_t)R * C, bps);
+  });
+}
+
+// Apply passes: the tiled kernel for C % 4 == 0, else the flat one (the callers have refused split planes there).  The caller checks
+// the launch.
+static void launch_apply_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y,
+                             void* y_split, int B, int R, int C, int act, float slope, int fmt, hipStream_t s) {
+  const size_t bxs = (size_t)R * C;
+  if (C % 4 == 0) {
+    const BnGrid g = bn_apply_grid(R, C);
+    hipLaunchKernelGGL(bn_act_fwd_tiled_kernel, dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, y,
+                       (u16_t*)y_split, R, C, g.rows_per_chunk, act, slope, bxs, fmt);
+  } else {
+    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(grid_for(bxs / 4 + 1, 256), 1, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, y, bxs, C,
+                       act, slope, bxs);
   }
-  for (; r < r1; r += BN_TY) {
-    const float* p = u + (size_t)r * C2 + c;
-    emit(r, need_u ? pair_ld4<VEC>(p, nv) : zero, need_u ? pair_ld4<VEC>(p + C, nv) : zero, pair_ld4<VEC>(dy + (size_t)r * C + c, nv));
+}
+static void launch_apply_bwd(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma, const float* beta,
+                             const float* sum_g, const float* sum_gx, float* dx, void* dx_split, int B, int R, int C, float invR, int act,
+                             float slope, int fmt, float scale, int* sat, hipStream_t s) {
+  const size_t bxs = (size_t)R * C;
+  if (C % 4 == 0) {
+    const BnGrid g = bn_apply_grid(R, C);
+    hipLaunchKernelGGL(bn_act_bwd_tiled_kernel, dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, x, dy, mean, rstd, gamma, beta, sum_g,
+                       sum_gx, dx, (u16_t*)dx_split, R, C, g.rows_per_chunk, invR, act, slope, bxs, fmt, scale, sat);
+  } else {
+    hipLaunchKernelGGL(bn_act_bwd_kernel, dim3(grid_for(bxs / 4 + 1, 256), 1, B), dim3(256), 0, s, x, dy, mean, rstd, gamma, beta, sum_g,
+                       sum_gx, dx, bxs, C, invR, act, slope, bxs);
   }
 }
 
@@ -819,51 +813,33 @@ using namespace vp;
 
 extern "C" {
 
-size_t vp_bn_workspace_bytes(int R, int C) { return bn_ws_floats(R, C) * sizeof(float); }
+size_t vp_bn_workspace_bytes(int R, int C) { return bn_ws_bytes(1, R, C); }
 
 int vp_bn_stats_f32(const float* x, int R, int C, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                     float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(x && mean && rstd && ws && R > 0 && C > 0, "vp_bn_stats_f32: bad arguments");
   if (ws_bytes < vp_bn_workspace_bytes(R, C)) return fail(VP_ERR_WORKSPACE, "vp_bn_stats_f32: workspace too small");
-  BnGrid g = bn_grid(R, C);
-  hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;
-  hipLaunchKernelGGL((bn_partial_kernel<0>), dim3(g.chunks_r, g.chunks_c), dim3(256), 0, s, x, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, R, C,
-                     g.rows_per_chunk, 0, 0.f);
-  int rc = check_launch("vp_bn_stats_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FIN_C - 1) / FIN_C), dim3(256), 0, s, (const float*)part, g.chunks_r, R, C, eps,
-                     momentum, mean, rstd, running_mean, running_var, x);
-  return check_launch("vp_bn_stats_f32(final)");
+  return launch_stats("vp_bn_stats_f32", x, 1, R, C, eps, momentum, mean, rstd, running_mean, running_var, ws, (hipStream_t)stream);
 }
 
 static int bn_act_fwd_impl(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y,
-                           void* y_split, int R, int C, int act, float slope, vp_stream stream, int fmt = SPLIT_BF16) {
+                           void* y_split, int R, int C, int act, float slope, vp_stream stream, int fmt) {
   VP_REQUIRE(fmt == SPLIT_BF16 || fmt == SPLIT_F16, "vp_bn_act_fwd_split_fmt_f32: format 0 (bf16 pair) or 1 (fp16 pair)");
   VP_REQUIRE(x && mean && rstd && (y || y_split) && R > 0 && C > 0, "vp_bn_act_fwd: bad arguments");
   VP_REQUIRE(!y_split || C % 4 == 0, "vp_bn_act_fwd_split_f32: C must be a multiple of 4");
-  const size_t n = (size_t)R * C;
-  if (C % 4 == 0) {
-    BnGrid g = bn_apply_grid(R, C);
-    hipLaunchKernelGGL(bn_act_fwd_tiled_kernel, dim3(g.chunks_r, g.chunks_c), dim3(256), 0, (hipStream_t)stream, x, mean, rstd,
-                       gamma, beta, y, (u16_t*)y_split, R, C, g.rows_per_chunk, act, slope, (size_t)0, fmt);
-  } else {
-    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, x, mean, rstd, gamma,
-                       beta, y, n, C, act, slope, (u16_t*)y_split);
-  }
+  launch_apply_fwd(x, mean, rstd, gamma, beta, y, y_split, 1, R, C, act, slope, fmt, (hipStream_t)stream);
   return check_launch("vp_bn_act_fwd");
 }
 
 int vp_bn_act_fwd_f32(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y,
                       int R, int C, int act, float slope, vp_stream stream) {
   VP_REQUIRE(y, "vp_bn_act_fwd_f32: y is null");
-  return bn_act_fwd_impl(x, mean, rstd, gamma, beta, y, nullptr, R, C, act, slope, stream);
+  return bn_act_fwd_impl(x, mean, rstd, gamma, beta, y, nullptr, R, C, act, slope, stream, SPLIT_BF16);
 }
 
 int vp_bn_act_fwd_split_f32(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
                             float* y, void* y_split, int R, int C, int act, float slope, vp_stream stream) {
-  return bn_act_fwd_impl(x, mean, rstd, gamma, beta, y, y_split, R, C, act, slope, stream);
+  return bn_act_fwd_impl(x, mean, rstd, gamma, beta, y, y_split, R, C, act, slope, stream, SPLIT_BF16);
 }
 
 int vp_bn_act_fwd_split_fmt_f32(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta,
@@ -873,36 +849,17 @@ int vp_bn_act_fwd_split_fmt_f32(const float* x, const float* mean, const float* 
 
 static int bn_act_bwd_impl(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
                            const float* beta, float* dx, void* dx_split, float* dgamma, float* dbeta, int R, int C, int act,
-                           float slope, int batch_stats, void* ws, size_t ws_bytes, vp_stream stream, int fmt = SPLIT_BF16,
-                           float scale = 1.f, int* sat = nullptr) {
+                           float slope, int batch_stats, void* ws, size_t ws_bytes, vp_stream stream, int fmt, float scale, int* sat) {
   VP_REQUIRE(x && dy && mean && rstd && (dx || dx_split) && ws && R > 0 && C > 0, "vp_bn_act_bwd_f32: bad arguments");
   VP_REQUIRE((fmt == SPLIT_BF16 || fmt == SPLIT_F16) && scale > 0.f, "vp_bn_act_bwd_split_fmt_f32: format 0 | 1, scale > 0");
   VP_REQUIRE(!dx_split || C % 4 == 0, "vp_bn_act_bwd_split_f32: C must be a multiple of 4");
   if (ws_bytes < vp_bn_workspace_bytes(R, C)) return fail(VP_ERR_WORKSPACE, "vp_bn_act_bwd_f32: workspace too small");
-  BnGrid g = bn_grid(R, C);
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;
-  float* sum_g = part + (size_t)2 * g.chunks_r * C;
-  float* sum_gx = sum_g + C;
-  hipLaunchKernelGGL((bn_partial_kernel<1>), dim3(g.chunks_r, g.chunks_c), dim3(256), 0, s, x, dy, mean, rstd, gamma, beta, part,
-                     R, C, g.rows_per_chunk, act, slope);
-  int rc = check_launch("vp_bn_act_bwd_f32(partial)");
+  int rc = launch_bn_bwd_sums("vp_bn_act_bwd_f32", x, dy, mean, rstd, gamma, beta, dgamma, dbeta, 1, R, C, act, slope, ws, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FIN_C - 1) / FIN_C), dim3(256), 0, s, (const float*)part, g.chunks_r, C, sum_g, sum_gx,
-                     dgamma, dbeta);
-  rc = check_launch("vp_bn_act_bwd_f32(final)");
-  if (rc) return rc;
-  const size_t n = (size_t)R * C;
-  const float invR = batch_stats ? 1.f / (float)R : 0.f;
-  if (C % 4 == 0) {
-    BnGrid ga = bn_apply_grid(R, C);
-    hipLaunchKernelGGL(bn_act_bwd_tiled_kernel, dim3(ga.chunks_r, ga.chunks_c), dim3(256), 0, s, x, dy, mean, rstd, gamma, beta,
-                       (const float*)sum_g, (const float*)sum_gx, dx, (u16_t*)dx_split, R, C, ga.rows_per_chunk, invR, act, slope,
-                       (size_t)0, fmt, scale, sat);
-  } else {
-    hipLaunchKernelGGL(bn_act_bwd_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, s, x, dy, mean, rstd, gamma, beta,
-                       (const float*)sum_g, (const float*)sum_gx, dx, n, C, invR, act, slope, (u16_t*)dx_split);
-  }
+  const BnWs w = bn_ws(1, R, C);
+  launch_apply_bwd(x, dy, mean, rstd, gamma, beta, (const float*)ws + w.sum_g, (const float*)ws + w.sum_gx, dx, dx_split, 1, R, C,
+                   batch_stats ? 1.f / (float)R : 0.f, act, slope, fmt, scale, sat, s);
   return check_launch("vp_bn_act_bwd_f32(apply)");
 }
 
@@ -910,14 +867,15 @@ int vp_bn_act_bwd_f32(const float* x, const float* dy, const float* mean, const 
                       const float* beta, float* dx, float* dgamma, float* dbeta, int R, int C, int act, float slope,
                       int batch_stats, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(dx, "vp_bn_act_bwd_f32: dx is null");
-  return bn_act_bwd_impl(x, dy, mean, rstd, gamma, beta, dx, nullptr, dgamma, dbeta, R, C, act, slope, batch_stats, ws, ws_bytes, stream);
+  return bn_act_bwd_impl(x, dy, mean, rstd, gamma, beta, dx, nullptr, dgamma, dbeta, R, C, act, slope, batch_stats, ws, ws_bytes, stream,
+                         SPLIT_BF16, 1.f, nullptr);
 }
 
 int vp_bn_act_bwd_split_fmt_f32(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
                                 const float* beta, float* dx, void* dx_split, float* dgamma, float* dbeta, int R, int C, int act,
                                 float slope, int batch_stats, int fmt, float scale, void* ws, size_t ws_bytes, vp_stream stream) {
   return bn_act_bwd_impl(x, dy, mean, rstd, gamma, beta, dx, dx_split, dgamma, dbeta, R, C, act, slope, batch_stats, ws, ws_bytes, stream,
-                         fmt, scale);
+                         fmt, scale, nullptr);
 }
 
 int vp_bn_act_bwd_split_fmt_sat_f32(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
@@ -931,39 +889,22 @@ int vp_bn_act_bwd_split_fmt_sat_f32(const float* x, const float* dy, const float
 int vp_bn_act_bwd_split_f32(const float* x, const float* dy, const float* mean, const float* rstd, const float* gamma,
                             const float* beta, float* dx, void* dx_split, float* dgamma, float* dbeta, int R, int C, int act,
                             float slope, int batch_stats, void* ws, size_t ws_bytes, vp_stream stream) {
-  return bn_act_bwd_impl(x, dy, mean, rstd, gamma, beta, dx, dx_split, dgamma, dbeta, R, C, act, slope, batch_stats, ws, ws_bytes, stream);
+  return bn_act_bwd_impl(x, dy, mean, rstd, gamma, beta, dx, dx_split, dgamma, dbeta, R, C, act, slope, batch_stats, ws, ws_bytes, stream,
+                         SPLIT_BF16, 1.f, nullptr);
 }
 
 // ---- nn.InstanceNorm2d(affine=False) + activation: the same kernels with blockIdx.z = image (models/blocks.py:22) --------
-size_t vp_instnorm_workspace_bytes(int B, int R, int C) { return (size_t)B * bn_ws_floats(R, C) * sizeof(float); }
+size_t vp_instnorm_workspace_bytes(int B, int R, int C) { return bn_ws_bytes(B, R, C); }
 
 static int instnorm_act_fwd_impl(const float* x, float* y, void* y_split, float* mean, float* rstd, int B, int R, int C, float eps, int act,
                                  float slope, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(x && y && mean && rstd && ws && B > 0 && R > 0 && C > 0, "vp_instnorm_act_fwd_f32: bad arguments");
   VP_REQUIRE(!y_split || C % 4 == 0, "vp_instnorm_act_fwd_split_f32: C must be a multiple of 4");
   if (ws_bytes < vp_instnorm_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_instnorm_act_fwd_f32: workspace too small");
-  const BnGrid g = bn_grid(R, C);
-  const size_t bxs = (size_t)R * C, bps = (size_t)2 * g.chunks_r * C;
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;
-  hipLaunchKernelGGL((bn_partial_kernel<0>), dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, x, (const float*)nullptr,
-                     (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, R, C,
-                     g.rows_per_chunk, 0, 0.f, bxs, bps);
-  int rc = check_launch("vp_instnorm_act_fwd_f32(partial)");
+  int rc = launch_stats("vp_instnorm_act_fwd_f32", x, B, R, C, eps, 0.f, mean, rstd, nullptr, nullptr, ws, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, g.chunks_r, R, C,
-                     eps, 0.f, mean, rstd, (float*)nullptr, (float*)nullptr, x, bps, bxs);
-  rc = check_launch("vp_instnorm_act_fwd_f32(final)");
-  if (rc) return rc;
-  if (C % 4 == 0) {
-    const BnGrid ga = bn_apply_grid(R, C);
-    hipLaunchKernelGGL(bn_act_fwd_tiled_kernel, dim3(ga.chunks_r, ga.chunks_c, B), dim3(256), 0, s, x, (const float*)mean,
-                       (const float*)rstd, (const float*)nullptr, (const float*)nullptr, y, (u16_t*)y_split, R, C, ga.rows_per_chunk,
-                       act, slope, bxs);
-  } else {
-    hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(grid_for(bxs / 4 + 1, 256), 1, B), dim3(256), 0, s, x, (const float*)mean,
-                       (const float*)rstd, (const float*)nullptr, (const float*)nullptr, y, bxs, C, act, slope, (u16_t*)nullptr, bxs);
-  }
+  launch_apply_fwd(x, mean, rstd, nullptr, nullptr, y, y_split, B, R, C, act, slope, SPLIT_BF16, s);
   return check_launch("vp_instnorm_act_fwd_f32(apply)");
 }
 
@@ -983,30 +924,12 @@ static int instnorm_act_bwd_impl(const float* x, const float* dy, const float* m
   VP_REQUIRE(x && dy && mean && rstd && dx && ws && B > 0 && R > 0 && C > 0, "vp_instnorm_act_bwd_f32: bad arguments");
   VP_REQUIRE(!dx_split || C % 4 == 0, "vp_instnorm_act_bwd_split_f32: C must be a multiple of 4");
   if (ws_bytes < vp_instnorm_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_instnorm_act_bwd_f32: workspace too small");
-  const BnGrid g = bn_grid(R, C);
-  const size_t bxs = (size_t)R * C, bps = (size_t)2 * g.chunks_r * C;
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)ws;
-  float* sum_g = part + (size_t)B * bps;          // [B][C], then sum_gx [B][C]
-  float* sum_gx = sum_g + (size_t)B * C;
-  hipLaunchKernelGGL((bn_partial_kernel<1>), dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, x, dy, mean, rstd, (const float*)nullptr,
-                     (const float*)nullptr, part, R, C, g.rows_per_chunk, act, slope, bxs, bps);
-  int rc = check_launch("vp_instnorm_act_bwd_f32(partial)");
+  int rc = launch_bn_bwd_sums("vp_instnorm_act_bwd_f32", x, dy, mean, rstd, nullptr, nullptr, nullptr, nullptr, B, R, C, act, slope, ws, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, g.chunks_r, C, sum_g,
-                     sum_gx, (float*)nullptr, (float*)nullptr, bps);
-  rc = check_launch("vp_instnorm_act_bwd_f32(final)");
-  if (rc) return rc;
-  const float invR = 1.f / (float)R;
-  if (C % 4 == 0) {
-    const BnGrid ga = bn_apply_grid(R, C);
-    hipLaunchKernelGGL(bn_act_bwd_tiled_kernel, dim3(ga.chunks_r, ga.chunks_c, B), dim3(256), 0, s, x, dy, mean, rstd,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)sum_g, (const float*)sum_gx, dx, (u16_t*)dx_split, R, C,
-                       ga.rows_per_chunk, invR, act, slope, bxs);
-  } else {
-    hipLaunchKernelGGL(bn_act_bwd_kernel, dim3(grid_for(bxs / 4 + 1, 256), 1, B), dim3(256), 0, s, x, dy, mean, rstd, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)sum_g, (const float*)sum_gx, dx, bxs, C, invR, act, slope, (u16_t*)nullptr, bxs);
-  }
+  const BnWs w = bn_ws(B, R, C);
+  launch_apply_bwd(x, dy, mean, rstd, nullptr, nullptr, (const float*)ws + w.sum_g, (const float*)ws + w.sum_gx, dx, dx_split, B, R, C,
+                   1.f / (float)R, act, slope, SPLIT_BF16, 1.f, nullptr, s);
   return check_launch("vp_instnorm_act_bwd_f32(apply)");
 }
 
@@ -1022,7 +945,7 @@ int vp_instnorm_act_bwd_split_f32(const float* x, const float* dy, const float* 
 }
 
 // ---- label-gated pair: InstanceNorm statistics over the 2C stacked channels, then one blend pass ---------------------------------
-size_t vp_pair_blend_workspace_bytes(int B, int R, int C) { return (size_t)B * bn_ws_floats(R, 2 * C) * sizeof(float); }
+size_t vp_pair_blend_workspace_bytes(int B, int R, int C) { return bn_ws_bytes(B, R, 2 * C); }
 
 int vp_pair_blend_fwd_f32(const float* u, const float* label, float* y, void* y_split, float* mean, float* rstd, int B, int R, int C,
                           int norm, float eps, int act, float slope, void* ws, size_t ws_bytes, vp_stream stream) {
@@ -1032,18 +955,7 @@ int vp_pair_blend_fwd_f32(const float* u, const float* label, float* y, void* y_
   hipStream_t s = (hipStream_t)stream;
   if (norm) {
     if (ws_bytes < vp_pair_blend_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_pair_blend_fwd_f32: workspace too small");
-    const int C2 = 2 * C;
-    const BnGrid g = bn_grid(R, C2);
-    const size_t bxs = (size_t)R * C2, bps = (size_t)2 * g.chunks_r * C2;
-    float* part = (float*)ws;
-    hipLaunchKernelGGL((bn_partial_kernel<0>), dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, u, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, part, R, C2,
-                       g.rows_per_chunk, 0, 0.f, bxs, bps);
-    int rc = check_launch("vp_pair_blend_fwd_f32(partial)");
-    if (rc) return rc;
-    hipLaunchKernelGGL(bn_stats_final_kernel, dim3((C2 + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, g.chunks_r, R, C2,
-                       eps, 0.f, mean, rstd, (float*)nullptr, (float*)nullptr, u, bps, bxs);
-    rc = check_launch("vp_pair_blend_fwd_f32(final)");
+    int rc = launch_stats("vp_pair_blend_fwd_f32", u, B, R, 2 * C, eps, 0.f, mean, rstd, nullptr, nullptr, ws, s);
     if (rc) return rc;
   }
   const BnGrid ga = bn_apply_grid(R, C);
@@ -1069,26 +981,19 @@ int vp_pair_blend_bwd_f32(const float* u, const float* dy, const float* label, c
   const float* sum_gx = nullptr;
   if (norm) {
     if (ws_bytes < vp_pair_blend_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_pair_blend_bwd_f32: workspace too small");
-    const int C2 = 2 * C;
-    const BnGrid g = bn_grid(R, C2);                  // row chunks and slab layout of the 2C-channel InstanceNorm backward
-    const size_t bps = (size_t)2 * g.chunks_r * C2;
-    float* part = (float*)ws;
-    float* sg = part + (size_t)B * bps;               // [B][2C], then sum_gx [B][2C]
-    float* sgx = sg + (size_t)B * C2;
-    const dim3 grid(g.chunks_r, (C + BN_CH - 1) / BN_CH, B);
-    if (vec)
-      hipLaunchKernelGGL((pair_blend_partial_kernel<true>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, part, R, C, g.rows_per_chunk,
-                         act, slope, bps);
-    else
-      hipLaunchKernelGGL((pair_blend_partial_kernel<false>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, part, R, C, g.rows_per_chunk,
-                         act, slope, bps);
-    int rc = check_launch("vp_pair_blend_bwd_f32(partial)");
+    // row chunks and slab layout of the 2C-channel InstanceNorm backward; one block covers 64 channels of both branches
+    int rc = launch_bwd_sums("vp_pair_blend_bwd_f32", B, R, 2 * C, nullptr, nullptr, ws, s, [&](const BnGrid& g, float* part, size_t bps) {
+      const dim3 grid(g.chunks_r, (C + BN_CH - 1) / BN_CH, B);
+      if (vec)
+        hipLaunchKernelGGL((pair_blend_partial_kernel<true>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, part, R, C, g.rows_per_chunk,
+                           act, slope, bps);
+      else
+        hipLaunchKernelGGL((pair_blend_partial_kernel<false>), grid, dim3(256), 0, s, u, dy, label, mean, rstd, part, R, C, g.rows_per_chunk,
+                           act, slope, bps);
+    });
     if (rc) return rc;
-    hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C2 + FIN_C - 1) / FIN_C, 1, B), dim3(256), 0, s, (const float*)part, g.chunks_r, C2, sg,
-                       sgx, (float*)nullptr, (float*)nullptr, bps);
-    rc = check_launch("vp_pair_blend_bwd_f32(final)");
-    if (rc) return rc;
-    sum_g = sg; sum_gx = sgx;
+    const BnWs w = bn_ws(B, R, 2 * C);
+    sum_g = (const float*)ws + w.sum_g; sum_gx = (const float*)ws + w.sum_gx;
   }
   const BnGrid ga = bn_apply_grid(R, C);
   const dim3 grid(ga.chunks_r, ga.chunks_c, B);

@@ -86,7 +86,8 @@ class FusedVAEStep:
         env = os.environ.get
         fwd, bwd = _Plan(), _Plan()
         P = _ptr
-        # sticky device flag: a producer of fp16 gradient planes clamped a value (|g| * grad_scale16 > 65504); read in sync_counters()
+        # sticky device flag: the BatchNorm backward clamped a value of its fp16 gradient planes (|g| * grad_scale16 > 65504); read in
+        # sync_counters()
         self._f16_sat = torch.zeros(1, dtype=torch.int32, device=self.dev)
         x3 = self.precision in ("bf16x3", "f16x2")
         # Weight gradients go to a side stream (bf16x3 plans): they only feed the optimiser, so they can run underneath
@@ -253,8 +254,10 @@ class FusedVAEStep:
 
     def sync_counters(self):
         """Advance BatchNorm ``num_batches_tracked`` buffers (bookkeeping only; kept off the hot path).  precision="f16x2": also reads
-        the sticky saturation flag of the fp16 gradient planes (a host sync, like everything here) and raises when a step since the
-        last call clamped a gradient at +-65504 / grad_scale16 -- the weights of those steps are off; lower ``grad_scale16``."""
+        the sticky saturation flag (a host sync, like everything here) and raises when a step since the last call clamped a gradient at
+        +-65504 / grad_scale16 -- the weights of those steps are off; lower ``grad_scale16``.  The flag covers the fp16 gradient planes
+        that the BatchNorm backward writes (csrc/bn.hip's tiled kernel, the only one with split planes); the planes of dlogit and of
+        the NCHW -> NHWC pass do not report (``f16_saturated()`` counts clamped elements in whatever planes are still held)."""
         n = getattr(self, "_steps_since_sync", 0)
         if n:
             for m in self._bn_mods:

@@ -330,6 +330,22 @@ int vp_latent_fwd_f32(const float* mu, const float* logvar, const float* eps, fl
 int vp_latent_bwd_f32(const float* mu, const float* logvar, const float* eps, const float* dz, const float* gkl,
                       float gkl_scalar, float* dmu, float* dlogvar, int B, int Z, vp_stream stream);
 
+/* ---- per-image scoring of a trained VAE (vae_play_amd.infer.FusedVAEInference.score) --------- */
+/* The reference has no evaluation loop with a loss; the terms are its KL (models/networks.py:270) and the per-pixel
+ * F.binary_cross_entropy(reduction="sum"), kept per image.  Bit-reproducible: fixed-order sums, no atomics. */
+/* out[r] = sum_i -[t*max(log p,-100) + (1-t)*max(log(1-p),-100)] over the n elements of row r: p and t dense [rows][n] in the
+ * same memory order; the clamp of vp_bce_sum_f32.  ws >= vp_bce_rows_workspace_bytes(rows, n) = rows * ceil(n / 4096) floats. */
+size_t vp_bce_rows_workspace_bytes(int rows, int n);
+int vp_bce_rows_f32(const float* p, const float* t, int rows, int n, float* out, void* ws, size_t ws_bytes, vp_stream stream);
+/* z and kl exactly as vp_latent_fwd_f32 writes them (the same bits; kl may be NULL), and the log density ratio of the draw
+ * lr[b] = log p(z_b) - log q(z_b|x_b) = -1/2 sum_j z_j^2 + 1/2 sum_j (eps_j^2 + logvar_j)   (the 2 pi terms cancel) */
+int vp_latent_iw_fwd_f32(const float* mu, const float* logvar, const float* eps, float* z, float* kl, float* lr,
+                         int B, int Z, vp_stream stream);
+/* K-sample importance-weighted bound (Burda et al. 2016; new functionality, no counterpart in the reference).
+ * nbce, lr [B][K]: logw[b][k] = -nbce[b][k] + lr[b][k] (logw may be NULL);
+ * iwae[b] = max_k logw + log(sum_k exp(logw - max)) - log K; K = 1 returns logw[b][0] exactly */
+int vp_iw_bound_f32(const float* nbce, const float* lr, int B, int K, float* logw, float* iwae, vp_stream stream);
+
 /* ---- per-pixel BCE ------------------------------------------------------------------------ */
 /* out[0] = sum_i -[t*max(log p,-100) + (1-t)*max(log(1-p),-100)]  (torch F.binary_cross_entropy,
  * reduction='sum'; call form train_BE_font.py:107).  p and t may have different memory order only

@@ -12,9 +12,13 @@ Each figure is the median over ``--reps`` windows of ``--iters`` calls, a window
 inside every repetition, and min / max over the repetitions are reported as the spread.  Every variant is warmed up first.
 
 ``--layers`` adds, for every BatchNorm-followed 5x5 layer of the shape, the fused launch against convolution + normalise pass on
-preallocated buffers (the per-layer evidence for which form the plan keeps).  The result is one JSON document (``--out``).
+preallocated buffers (the per-layer evidence for which form the plan keeps).  ``--score K`` adds, at the benchmark shape, scored
+images/s of ``FusedVAEInference.score`` with 1 and K draws per image (eager and replayed) against the composed path: the modules
+in eval mode, then per-image BCE, density ratio and log-sum-exp in ATen (key ``score``; the other keys are unchanged).  The result
+is one JSON document (``--out``).
 
     python tools/bench_infer.py --out bench_out/infer.json
+    python tools/bench_infer.py --score 8 --score-only --out bench_out/infer_score.json
 """
 import argparse
 import json
@@ -104,6 +108,65 @@ def bench_shape(name, C, S, z, B, prec, args):
     return out
 
 
+def bench_score(name, C, S, z, B, prec, args):
+    """``--score K``: scored images/s with 1 and K draws per image -- FusedVAEInference.score (eager, and replayed as a hipGraph)
+    against the composed path in the same process: the modules in eval mode (encoder once, reparameterise + decoder per draw),
+    then per-image BCE, density ratio and log-sum-exp in ATen"""
+    import math
+    import torch.nn.functional as F
+    import vae_play_amd as V
+    torch.manual_seed(0)
+    vae = V.VAE(S, z, C).cuda().eval()
+    randomise_bn(vae, 1)
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand((B, C, S, S), generator=g).cuda()
+    out = {}
+    V.set_conv_precision(prec)
+    try:
+        with torch.no_grad():
+            for k in sorted({1, args.score}):
+                eps = torch.randn((B, k, z), generator=g).cuda()
+                eps_k = [eps[:, j].contiguous() for j in range(k)]
+                eager = V.FusedVAEInference(vae, B, S, C, precision=prec)
+                graph = V.FusedVAEInference(vae, B, S, C, precision=prec)
+                graph.enable_scoring(k)
+                graph.score(x, k, eps)
+                graph.capture()
+
+                def composed():
+                    mu, logvar = vae.encoder(x)
+                    kl = -0.5 * (1.0 + logvar - mu * mu - torch.exp(logvar)).sum(1)
+                    bce, lr = [], []
+                    for e in eps_k:
+                        zz = V.reparameterize(mu, logvar, eps=e)
+                        bce.append(F.binary_cross_entropy(vae.decoder(zz), x, reduction="none").flatten(1).sum(1))
+                        lr.append(-0.5 * (zz * zz).sum(1) + 0.5 * (e * e + logvar).sum(1))
+                    bce, lr = torch.stack(bce, 1), torch.stack(lr, 1)
+                    logw = lr - bce
+                    return {"bce": bce, "kl": kl, "logw": logw, "elbo": -(bce.mean(1) + kl), "iwae": torch.logsumexp(logw, 1) - math.log(k)}
+
+                ref, got = composed(), eager.score(x, k, eps)
+                r = ab({"composed": composed, "fused": lambda: eager.score(x, k, eps), "fused_graph": lambda: graph.score(x, k, eps)},
+                       args.iters, args.reps, args.warmup)
+                for v in r.values():
+                    v["scored_images_per_s"] = B / (v["ms"] * 1e-3)
+                # the paths compute the same thing (recorded, not asserted: the parity tests assert)
+                r["max_rel_diff_fused_vs_composed_iwae"] = ((got["iwae"] - ref["iwae"]).abs() / ref["iwae"].abs()).max().item()
+                # graph against eager AFTER the timing loops: a replay was seen to drift from the eager list with such a history
+                # (DESIGN.md section 14.1) while it is bit-identical right after capture()
+                after_e, after_g = eager.score(x, k, eps), graph.score(x, k, eps)
+                r["graph_equals_eager"] = all(bool(torch.equal(after_g[t], after_e[t])) for t in after_e)
+                r["eager_equals_its_first_call"] = all(bool(torch.equal(after_e[t], got[t])) for t in got)
+                r["max_rel_diff_graph_vs_eager"] = {t: ((after_g[t] - after_e[t]).abs() / after_e[t].abs()).max().item() for t in after_e}
+                out[f"k{k}"] = r
+                print(f"{name} {prec} score k={k}: composed {r['composed']['ms']:.3f} ms [{r['composed']['min']:.3f}, {r['composed']['max']:.3f}]  "
+                      f"fused {r['fused']['ms']:.3f} [{r['fused']['min']:.3f}, {r['fused']['max']:.3f}]  "
+                      f"graph {r['fused_graph']['ms']:.3f} [{r['fused_graph']['min']:.3f}, {r['fused_graph']['max']:.3f}]", flush=True)
+    finally:
+        V.set_conv_precision("f32")
+    return out
+
+
 def bench_layers(C, S, z, B, prec, args):
     """fused launch vs convolution + normalise pass, per BatchNorm-followed 5x5 layer, on preallocated buffers"""
     import vae_play_amd as V
@@ -171,6 +234,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5, help="windows per variant (alternating)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--layers", action="store_true", help="per-layer fused launch vs convolution + normalise pass")
+    ap.add_argument("--score", type=int, default=0, metavar="K",
+                    help="add the scoring leg at 128x128x3 batch 32: score() with 1 and K draws against the composed path")
+    ap.add_argument("--score-only", action="store_true", help="with --score: skip the reconstruct / decode / encode legs")
     ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated subset of: " + ", ".join(SHAPES))
     ap.add_argument("--precisions", default="bf16x3,f32")
     ap.add_argument("--out", default="bench_out/infer.json")
@@ -180,7 +246,14 @@ def main():
     doc = {"tool": "tools/bench_infer.py", "device": torch.cuda.get_device_name(0), "iters": args.iters, "reps": args.reps,
            "timing": "device events around a window of calls (host gaps included); median [min, max] over alternating repetitions",
            "results": {}, "layers": {}}
-    for name in args.shapes.split(","):
+    if args.score < 0 or (args.score_only and not args.score):
+        raise SystemExit("--score takes a positive K; --score-only needs it")
+    if args.score:
+        doc["score"] = {}
+        name = "bench_128x128x3_z128_b32"
+        for prec in args.precisions.split(","):
+            doc["score"][f"{name}/{prec}"] = bench_score(name, *SHAPES[name], prec, args)
+    for name in args.shapes.split(",") if not args.score_only else ():
         C, S, z, B = SHAPES[name]
         for prec in args.precisions.split(","):
             doc["results"][f"{name}/{prec}"] = bench_shape(name, C, S, z, B, prec, args)

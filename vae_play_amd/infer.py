@@ -12,9 +12,15 @@ launch splits K, and the first encoder block on its im2col) keep convolution + o
 Reference paths replaced: the ``eval()`` branch of VaeGan.forward (models/networks.py:248-258: sample and decode; encode ->
 reparameterise -> decode), the ``torch.no_grad()`` reconstruction inside the training loop (train.py:95-96), and the plain-VAE
 composition of Encoder (models/networks.py:72-78), reparameterize (:228-231) and Decoder (:107-112).
+
+``score`` adds what validation, model comparison and anomaly scoring need: per image the reconstruction term (the reference's
+per-pixel ``F.binary_cross_entropy``, summed over the image), the KL term (models/networks.py:270), their sum (the ELBO) and the
+K-sample importance-weighted bound.  The reference has no evaluation loop with a loss; the importance-weighted bound is new
+functionality, not a port.  It reuses the launches above -- encode once, decode K times -- plus the three kernels of csrc/score.hip.
 """
 from __future__ import annotations
 
+from types import SimpleNamespace
 from typing import Dict, Optional
 
 import torch
@@ -24,7 +30,7 @@ from .plan import PlanBuilder, _Plan, _ptr, plan_device
 
 
 class FusedVAEInference:
-    """encode / decode / reconstruct / sample for a ``networks.VAE`` (or an Encoder / Decoder pair: ``from_modules``).
+    """encode / decode / reconstruct / sample / score for a ``networks.VAE`` (or an Encoder / Decoder pair: ``from_modules``).
 
     The plan SNAPSHOTS the model when it is built: convolution weights are packed into plan-owned buffers and every BatchNorm's
     running statistics and affine parameters are folded into plan-owned scale / shift / rstd vectors, once, not per call.  After the
@@ -64,6 +70,7 @@ class FusedVAEInference:
         self.dev = plan_device(encoder, "FusedVAEInference", plan_only)
         self._bufs: Dict[str, torch.Tensor] = {}
         self._graphs: Dict[str, "torch.cuda.CUDAGraph"] = {}
+        self._score: Optional[SimpleNamespace] = None       # the scoring buffers: none until enable_scoring() / the first score()
         self._build()
         if not plan_only:
             self.refresh()
@@ -133,28 +140,32 @@ class FusedVAEInference:
             plan.run(s)
 
     def capture(self, warmup: int = 2):
-        """Capture encode, decode and reconstruct into one hipGraph each (linear launch lists, no allocation) and replay them from
-        then on; the results are bit-identical to the eager launches."""
+        """Capture encode, decode and reconstruct -- and the scoring lists built so far (``score``) -- into one hipGraph each
+        (linear launch lists, no allocation) and replay them from then on; the results are bit-identical to the eager launches.
+        A scoring list first used after this is captured when it is built."""
+        self._graphs = self._capture(list(self._plans), warmup)
+        return self._graphs
+
+    def _capture(self, names, warmup: int = 2):
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(warmup):
-                for which in self._plans:
+                for which in names:
                     self._run(which)
         torch.cuda.current_stream().wait_stream(side)
         graphs = {}
         ops.CAPTURE_OK[0] = True          # (ops._stream() refuses captures it does not know: the autograd front end's)
         try:
-            for which, plans in self._plans.items():
+            for which in names:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
                     s = torch.cuda.current_stream().cuda_stream
-                    for plan in plans:
+                    for plan in self._plans[which]:
                         plan.run(s)
                 graphs[which] = g
         finally:
             ops.CAPTURE_OK[0] = False
-        self._graphs = graphs
         return graphs
 
     def _check(self, t: torch.Tensor, what: str, tail) -> None:
@@ -219,6 +230,101 @@ class FusedVAEInference:
             mu[i0:i0 + m].copy_(self.mu[:m])
             logvar[i0:i0 + m].copy_(self.logvar[:m])
         return out, mu, logvar
+
+    # ---- scoring: per-image ELBO and importance-weighted bound -----------------------------------
+    def enable_scoring(self, k_max: int = 1) -> None:
+        """Allocate what ``score`` needs for up to ``k_max`` draws per image (``score`` calls this itself on first use, and again
+        when it is asked for more draws).  A plan that never scores owns none of it: ``_bufs`` and the encode / decode / reconstruct
+        lists of such a plan are what they were before scoring existed.  The buffers are registered like every other one
+        (``PlanBuilder.buf``); asking for more draws replaces them and drops the lists (and graphs) built over the old ones."""
+        k_max = int(k_max)
+        if k_max < 1:
+            raise ValueError("k_max must be positive")
+        if self._score is not None and k_max <= self._score.k_max:
+            return
+        for which in [w for w in self._plans if w.startswith("score")]:
+            del self._plans[which]
+            self._graphs.pop(which, None)
+        for name in [n for n in self._bufs if n.startswith("score.")]:
+            del self._bufs[name]
+        B, Z, n = self.B, self.Z, self.C * self.S * self.S
+        b = PlanBuilder(self, self.dev, self.precision, side_on=False, wgrad_cus=(0, 0))
+        s = SimpleNamespace(k_max=k_max, n=n)
+        s.eps = b.buf("score.eps", k_max, B, Z)                 # draw-major: draw j's eps is a dense [B][Z]
+        s.kl = b.buf("score.kl", B)
+        # what the per-draw launches write, [draw][image] ...
+        s.bce_kb, s.lr_kb = b.buf("score.bce_kb", k_max * B), b.buf("score.lr_kb", k_max * B)
+        # ... and the same [image][draw], as vp_iw_bound_f32 reads it (one draw: the two orders are one)
+        s.bce_bk, s.lr_bk = (b.buf("score.bce_bk", B * k_max), b.buf("score.lr_bk", B * k_max)) if k_max > 1 else (s.bce_kb, s.lr_kb)
+        s.logw, s.iwae = b.buf("score.logw", B * k_max), b.buf("score.iwae", B)
+        s.ws = b.ws("score.bce.ws", b.lib.vp_bce_rows_workspace_bytes(B, n))
+        self._score = s
+
+    def _score_bk(self, k: int):
+        """the (bce, lr) buffers in [image][draw] order for k draws (one draw: the per-draw buffers themselves)"""
+        s = self._score
+        return (s.bce_kb, s.lr_kb) if k == 1 else (s.bce_bk, s.lr_bk)
+
+    def _score_list(self, k: int) -> str:
+        """name of the launch list that scores one chunk with k draws: the encode list once; per draw the reparameterisation with
+        its log density ratio, the decode list and the per-image BCE; then the bound.  Built on first use."""
+        which = f"score{k}"
+        if which in self._plans:
+            return which
+        P, s, B = _ptr, self._score, self.B
+        (p_enc,), (p_dec,) = self._plans["encode"], self._plans["decode"]
+        plans = [p_enc]
+        for j in range(k):
+            lat, bce = _Plan(), _Plan()
+            lat.add("vp_latent_iw_fwd_f32", P(self.mu), P(self.logvar), P(s.eps[j]), P(self.z), P(s.kl) if j == 0 else None,
+                    P(s.lr_kb[j * B:]), B, self.Z)
+            bce.add("vp_bce_rows_f32", P(self.x_tilde), P(self.x_nchw), B, s.n, P(s.bce_kb[j * B:]), P(s.ws), s.ws.numel() * 4)
+            plans += [lat, p_dec, bce]
+        fin = _Plan()
+        bce_bk, lr_bk = self._score_bk(k)
+        if k > 1:       # [draw][image] -> [image][draw]: the transpose kernel over one k x B "image"
+            fin.add("vp_nchw_to_nhwc_f32", P(s.bce_kb), P(bce_bk), 1, k, B, 1)
+            fin.add("vp_nchw_to_nhwc_f32", P(s.lr_kb), P(lr_bk), 1, k, B, 1)
+        fin.add("vp_iw_bound_f32", P(bce_bk), P(lr_bk), B, k, P(s.logw), P(s.iwae))
+        self._plans[which] = tuple(plans + [fin])
+        if self._graphs:
+            self._graphs.update(self._capture([which]))
+        return which
+
+    def score(self, x: torch.Tensor, k: int = 1, eps: Optional[torch.Tensor] = None,
+              generator: Optional[torch.Generator] = None) -> Dict[str, torch.Tensor]:
+        """How well the model explains images x (n, C, S, S), with k draws z ~ q(z | x) per image, in nats:
+          bce  (n, k)  reconstruction term per image and draw: the per-pixel BCE summed over C * S * S
+          kl   (n,)    analytic KL(q(z | x) || N(0, I))    (models/networks.py:270)
+          logw (n, k)  log importance weight  log p(x | z) + log p(z) - log q(z | x)
+          elbo (n,)    -(mean_k bce + kl)
+          iwae (n,)    log-mean-exp_k logw: the k-sample importance-weighted bound (no counterpart in the reference)
+        ``eps`` (n, k, Z) may be injected, else it is drawn from N(0, I) with ``generator``.  The encoder runs once per chunk, the
+        decoder once per draw; ``score(x, 1, eps)`` decodes exactly what ``reconstruct(x, eps[:, 0])`` does."""
+        self._check(x, "x", (self.C, self.S, self.S))
+        n, k = x.shape[0], int(k)
+        if k < 1:
+            raise ValueError("k must be positive")
+        if eps is None:
+            eps = torch.randn((n, k, self.Z), dtype=torch.float32, device=x.device, generator=generator)
+        self._check(eps, "eps", (k, self.Z))
+        if eps.shape[0] != n:
+            raise _lib.VaePlayHipError(f"FusedVAEInference: eps has {eps.shape[0]} rows, x has {n}")
+        self.enable_scoring(k)
+        which, s, B = self._score_list(k), self._score, self.B
+        bce, logw = x.new_empty((n, k)), x.new_empty((n, k))
+        kl, iwae = x.new_empty((n,)), x.new_empty((n,))
+        for i0, m in self._chunks(n):
+            self._load(self.x_nchw, x[i0:i0 + m])
+            s.eps[:k, :m].copy_(eps[i0:i0 + m].transpose(0, 1), non_blocking=True)
+            if m < B:
+                s.eps[:k, m:].zero_()
+            self._run(which)
+            bce[i0:i0 + m].copy_(self._score_bk(k)[0][:B * k].view(B, k)[:m])
+            logw[i0:i0 + m].copy_(s.logw[:B * k].view(B, k)[:m])
+            kl[i0:i0 + m].copy_(s.kl[:m])
+            iwae[i0:i0 + m].copy_(s.iwae[:m])
+        return {"bce": bce, "kl": kl, "logw": logw, "elbo": -(bce.mean(1) + kl), "iwae": iwae}
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """x_p (n, C, S, S): decode z_p ~ N(0, I) (the reference's ``x is None`` branch)"""

@@ -407,6 +407,40 @@ def bce_sum(p, t):
     return out
 
 
+def bce_rows(p, t):
+    """out[r] = the BCE sum over row r of p, t (rows, ...): the per-image reconstruction term"""
+    assert _same_layout(p, t)
+    if not (p.is_contiguous() or _is_nhwc(p)):      # rows must be the outermost, dense dimension (either image order will do)
+        p, t = p.contiguous(), t.contiguous()
+    rows, n = p.shape[0], p.numel() // p.shape[0]
+    ws = _ws(_lib.load().vp_bce_rows_workspace_bytes(rows, n), p)
+    out = torch.empty((rows,), dtype=torch.float32, device=p.device)
+    _lib.call("vp_bce_rows_f32", _p(p), _p(t), rows, n, _p(out), _p(ws), ws.numel() * 4, _stream())
+    return out
+
+
+def latent_iw_fwd(mu, logvar, eps, want_kl: bool = True):
+    """(z, kl, lr): latent_fwd's z and kl (the same bits) and lr[b] = log p(z_b) - log q(z_b | x_b)"""
+    B, Z = mu.shape
+    mu, logvar, eps = mu.contiguous(), logvar.contiguous(), eps.contiguous()
+    z = torch.empty_like(mu)
+    kl = torch.empty((B,), dtype=torch.float32, device=mu.device) if want_kl else None
+    lr = torch.empty((B,), dtype=torch.float32, device=mu.device)
+    _lib.call("vp_latent_iw_fwd_f32", _p(mu), _p(logvar), _p(eps), _p(z), _p(kl), _p(lr), B, Z, _stream())
+    return z, kl, lr
+
+
+def iw_bound(nbce, lr, want_logw: bool = True):
+    """(logw, iwae) of nbce, lr (B, K): logw = lr - nbce, iwae[b] = log-mean-exp_k logw[b] (the K-sample importance-weighted bound)"""
+    B, K = nbce.shape
+    assert tuple(lr.shape) == (B, K)
+    nbce, lr = nbce.contiguous(), lr.contiguous()
+    logw = torch.empty_like(nbce) if want_logw else None
+    iwae = torch.empty((B,), dtype=torch.float32, device=nbce.device)
+    _lib.call("vp_iw_bound_f32", _p(nbce), _p(lr), B, K, _p(logw), _p(iwae), _stream())
+    return logw, iwae
+
+
 def bce_bwd(p, t, g: Optional[torch.Tensor], gscale: float = 1.0):
     assert _same_layout(p, t)
     dp = torch.empty_like(p)

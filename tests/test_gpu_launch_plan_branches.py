@@ -104,15 +104,44 @@ BRANCHES = {
     "wgrad_main_f16_k64": _wgrad(F16_2, 1, 4, 64, 64, 1, 3, route=W_MAIN, bk=64, fast=1),
 }
 
+# What the descriptor fillers of csrc/conv_exec.h fill beyond BRANCHES: the epilogue fields (bias, sigmoid, out_scale, running
+# statistics, the affine outputs), the generic-geometry descriptors (ks = 1, 3 and 4 x 4 stride 2) in the three 16-bit arithmetics,
+# the plain 5 x 5 stride-1 weight gradient and the fp32 entries outside the fast path.  Smallest shapes: 1 image, 4 x 4 small side.
+# Extra keys: ks, bias, act, out_scale, running (non-null running statistics), outputs ("f32" | "split" | "both", affine).
+def _with(case, **extra):
+    return dict(case, **extra)
+
+
+_TAG = {BF16X3: "bf16x3", F16_2: "f16_two_products", F16_3: "f16_three_products"}
+VARIANTS = {
+    "gather_bias_sigmoid": _with(_conv(0, BF16X3, 1, 4, 64, 8, 1, route=STAGED, nsplit=1), bias=1, act=4),
+    **{f"k{ks}_{('gather', 'scatter')[fam]}_{_TAG[ar]}": _with(_conv(fam, ar, 1, 4, 16, 8, st, route=STAGED, nsplit=1), ks=ks)
+       for ks, st in ((1, 1), (3, 1), (4, 2)) for fam in (0, 1) for ar in (BF16X3, F16_2, F16_3)},
+    "scatter_bias_plain5": _with(_conv(1, BF16X3, 1, 4, 8, 8, 1, route=STAGED), bias=1),
+    "scatter_bias_k4_stride2": _with(_conv(1, BF16X3, 1, 4, 8, 8, 2, route=STAGED, gz=4), ks=4, bias=1),
+    "f16_out_scale_gather": _with(_conv(0, F16_2, 1, 4, 64, 8, 1, route=STAGED), out_scale=1.0 / 16),
+    "stats_running_f16_two_products_gather": _with(_stats(0, F16_2, 1, 4, 8, 8, 1, route=STAGED), running=1),
+    "stats_running_f16_three_products_scatter": _with(_stats(1, F16_3, 1, 4, 8, 8, 1, route=STAGED), running=1),
+    "stats_running_f32_gather": _with(_stats(0, F32, 1, 4, 16, 64, 1, route=STAGED), running=1),
+    "affine_split_planes_only": _with(_affine(0, BF16X3, 1, 4, 64, 64, 1), outputs="split"),
+    "affine_both_outputs": _with(_affine(1, BF16X3, 1, 4, 64, 64, 2, gz=4, pair_phases=1), outputs="both"),
+    "affine_act_none": _with(_affine(0, F32, 1, 4, 32, 64, 1), act=0),
+    "wgrad_plain5_stride1_bf16x3": _wgrad(BF16X3, 1, 4, 64, 64, 1, 5, route=W_WIDE, kind=3),
+    "wgrad_plain5_stride1_f16": _wgrad(F16_2, 1, 4, 64, 64, 1, 5, route=W_MAIN),
+    "f32_legacy_gather": _conv(0, F32, 1, 4, 8, 8, 1, route=LEGACY),
+    "f32_scatter_bias_k4_stride2": _with(_conv(1, F32, 1, 4, 8, 8, 2), ks=4, bias=1),     # always igemm.h: no plan
+}
+
 
 def plan_of(planner, c):
     """the plan of a case, from tests/test_launch_plan.py's Planner"""
     S = c["S"]
+    Hb = S * c["stride"]
     if c["kind"] == "wgrad":
-        Hb = S if c["stride"] == 1 else 2 * S
         return planner.wgrad(c["arith"], c["B"], S, S, Hb, Hb, c["Cbig"], c["Csmall"], c["ks"], c["stride"], max_cus=c["max_cus"])
     epi = {"conv": 0, "stats": 1, "affine": 2}[c["kind"]]
-    return planner.conv(c["family"], c["arith"], c["B"], S, S, c["Cbig"], c["Csmall"], c["stride"], epi=epi)
+    return planner.conv(c["family"], c["arith"], c["B"], S, S, c["Cbig"], c["Csmall"], c["stride"], ks=c["ks"], Hb=Hb, Wb=Hb,
+                        has_bias=c.get("bias", 0), act=c.get("act", 0) if c["kind"] == "conv" else 0, epi=epi)
 
 
 def _nhwc(B, C, H, W, gen):
@@ -136,14 +165,16 @@ def _packed(w, arith, family):
         return ops.pack_w(w, family == 0, family == 1)[family]
     if arith == BF16X3:
         return ops.pack_w_split(w, family == 0, family == 1)[family]
+    if w.shape[2] != 5:      # no k x k packer writes fp16 pairs: the fp32 layout (a permutation), then the element-wise split
+        return ops.split_f32(ops.pack_w(w, family == 0, family == 1)[family], ops.SPLIT_F16)
     return ops.pack_w5_split(w, family == 0, family == 1, ops.SPLIT_F16)[family]
 
 
-def _act(t, arith):
+def _act(t, arith, scale=1.0):
     from vae_play_amd import ops
     if arith == F32:
         return t.contiguous(memory_format=torch.channels_last)
-    return ops.split_f32(t, ops.SPLIT_BF16 if arith == BF16X3 else ops.SPLIT_F16)
+    return ops.split_f32(t, ops.SPLIT_BF16 if arith == BF16X3 else ops.SPLIT_F16, scale)
 
 
 def run_case(name, c):
@@ -185,32 +216,52 @@ def run_case(name, c):
         fam = c["family"]
         a, Cout, Ho = (x, Cs, S) if fam == 0 else (y, Cb, Hb)
         out = g.out("out", B, Ho, Ho, Cout).permute(0, 3, 1, 2)
-        ain, wp = _act(a, ar), _packed(w, ar, fam)
+        out_scale = c.get("out_scale", 1.0)
+        ain, wp = _act(a, ar, 1.0 / out_scale), _packed(w, ar, fam)
         which = ("gather", "scatter")[fam]
         chans = (Cb, Cs) if fam == 0 else (Cs, Cb)
+        bias = torch.randn(Cout, device=DEV, generator=gen) * 0.1 if c.get("bias") else None
+        if bias is not None:
+            outs["bias"] = bias
         if c["kind"] == "conv":
-            scale = () if ar in (BF16X3, F32) else (1.0,)
-            bias_act = (None,) if fam == 0 else ()
-            _lib.call(f"vp_conv_{which}_{suffix}", ptr(ain), ptr(wp), *bias_act, P(out), B, S, S, Hb, Hb, *chans, 5, st,
-                      *((0,) if fam == 0 else ()), *products, *scale, stream)
+            scale = () if ar in (BF16X3, F32) else (out_scale,)
+            if fam == 0:
+                bias_act, entry = (P(bias),), f"vp_conv_gather_{suffix}"
+            else:
+                bias_act, entry = ((P(bias),), f"vp_conv_scatter_bias_{suffix}") if bias is not None else ((), f"vp_conv_scatter_{suffix}")
+            _lib.call(entry, ptr(ain), ptr(wp), *bias_act, P(out), B, S, S, Hb, Hb, *chans, ks, st,
+                      *((c.get("act", 0),) if fam == 0 else ()), *products, *scale, stream)
         elif c["kind"] == "stats":
             query = {"bf16x3": lib.vp_conv5_stats_workspace_bytes, "f16": lib.vp_conv5_stats_f16_workspace_bytes,
                      "f32": lib.vp_conv5_stats_f32_workspace_bytes}[suffix]
             ws, nbytes = g.ws("ws", query(fam, B, S, S, Cb, Cs, st))
             assert nbytes > 0, "the planner lists this shape as able to emit statistics"
             mean, rstd = g.out("mean", Cout), g.out("rstd", Cout)
+            rm = rv = None
+            if c.get("running"):
+                outs["running_mean0"] = torch.randn(Cout, device=DEV, generator=gen)
+                outs["running_var0"] = torch.rand(Cout, device=DEV, generator=gen) + 0.5
+                rm, rv = g.state("running_mean", outs["running_mean0"]), g.state("running_var", outs["running_var0"])
+                outs["running_mean"], outs["running_var"] = rm, rv
             _lib.call(f"vp_conv5_{which}_stats_{suffix}", ptr(ain), ptr(wp), P(out), B, S, S, *chans, st, *products, 1e-5, 0.9, P(mean), P(rstd),
-                      None, None, P(ws), nbytes, stream)
+                      P(rm), P(rv), P(ws), nbytes, stream)
             outs["mean"], outs["rstd"] = mean, rstd
         else:
             assert lib.vp_conv5_affine_supported(fam, 1 if ar == F32 else 0, B, S, S, Cb, Cs, st) == 1
             scale = torch.empty(Cout, device=DEV).uniform_(0.5, 1.5, generator=gen)
             scale[1::3] *= -1.0
             shift = torch.randn(Cout, device=DEV, generator=gen) * 0.2
-            _lib.call(f"vp_conv5_{which}_affine_{suffix}", ptr(ain), ptr(wp), P(scale), P(shift), P(out), None, B, S, S, *chans, st, ops.ACT_RELU,
-                      stream)
+            wanted = c.get("outputs", "f32")
+            if wanted != "f32":
+                outs["planes"] = g.planes("planes", out.numel())
+            if wanted == "split":
+                g.items = [it for it in g.items if it[0] != "out"]      # the fp32 output is not requested: nothing to check
+                out = None
+            _lib.call(f"vp_conv5_{which}_affine_{suffix}", ptr(ain), ptr(wp), P(scale), P(shift), P(out), PV(outs.get("planes")), B, S, S, *chans,
+                      st, c.get("act", ops.ACT_RELU), stream)
             outs["scale"], outs["shift"] = scale, shift
-        outs["out"] = out
+        if out is not None:
+            outs["out"] = out
     g.check()
     return outs, (x, y, w)
 
@@ -254,12 +305,70 @@ def test_branch_against_fp64_direct_sums(name):
         assert em <= 1e-5 and er <= 1e-5
 
 
-def digests():
+@pytest.mark.parametrize("name", list(VARIANTS))
+def test_variant_against_fp64_direct_sums(name):
+    """the references and bounds of the branch test; a bias is one more term (tests/test_gpu_conv_direct_kxk.py), the sigmoid is held to
+    OP_RTOL like tests/test_gpu_parity.py's, the split planes and the running statistics as in tests/test_gpu_conv_affine.py and
+    tests/test_gpu_properties.py"""
+    from vae_play_amd import ops
+    from tests.util import OP_RTOL, assert_close
+    c = VARIANTS[name]
+    outs, (x, y, w) = run_case(name, c)
+    mode, st, ks = MODE[c["arith"]], c["stride"], c["ks"]
+    if c["kind"] == "wgrad":
+        cs, cb = R.tile_channels(c["Csmall"]), R.tile_channels(c["Cbig"])
+        _within(name, outs["dw"][cs][:, cb], *R.wgrad_ref(x, y, cs, cb, ks, st, terms=True), mode)
+        return
+    fam, S = c["family"], c["S"]
+    pts = R.gather_points(c["B"], S, 3) if fam == 0 else R.scatter_points(c["B"], S * st, 3)
+    r, A, K = R.gather_ref(x, w, pts, st, terms=True) if fam == 0 else R.scatter_ref(y, w, pts, st, terms=True)
+    if "bias" in outs:
+        b64 = outs["bias"].double()
+        r, A, K = r + b64, A + b64.abs(), K + 1
+    if c["kind"] == "affine":
+        s64, t64 = outs["scale"].double()[None, :], outs["shift"].double()[None, :]
+        ref = r * s64 + t64
+        ref = torch.relu(ref) if c.get("act", ops.ACT_RELU) == ops.ACT_RELU else ref
+        bound = s64.abs() * R.tau(K, mode).to(r.device) * A + R.SAFETY * 2 * 2.0 ** -24 * ((r * s64).abs() + t64.abs())
+        if "out" in outs:
+            worst = ((R.take(outs["out"], pts) - ref).abs() / bound).max().item()
+            print(f"{name}: worst |v - ref| / bound = {worst:.3f}")
+            assert worst <= 1.0
+        if "planes" in outs:      # hi + lo keep 16 significant bits (csrc/split.h): that plus 2^-16 |v|
+            B, Ho, Cout = c["B"], S if fam == 0 else S * st, ref.shape[1]
+            rec = R.take(ops.unsplit(outs["planes"]).view(B, Ho, Ho, Cout).permute(0, 3, 1, 2), pts)
+            worst = ((rec - ref).abs() / (bound + 2.0 ** -16 * ref.abs())).max().item()
+            print(f"{name}: planes, worst |hi + lo - ref| / bound = {worst:.3f}")
+            assert worst <= 1.0
+            if "out" in outs:
+                assert torch.equal(outs["planes"], ops.split_f32(outs["out"].permute(0, 2, 3, 1).contiguous()).view(2, -1))
+        return
+    got = R.take(outs["out"], pts)
+    if c.get("act") == ops.ACT_SIGMOID:
+        print(f"{name}: sigmoid, rel err {assert_close(got, torch.sigmoid(r), OP_RTOL, name):.2e}")
+        return
+    _within(name, got, r, A, K, mode)
+    if c["kind"] == "stats":
+        out = outs["out"]
+        xd = out.double()
+        m64, v64 = xd.mean(dim=(0, 2, 3)), xd.var(dim=(0, 2, 3), unbiased=False)
+        sig = v64.sqrt()
+        assert ((outs["mean"].double() - m64).abs() / sig).max().item() <= 1e-5
+        assert ((outs["rstd"].double() - (v64 + 1e-5).rsqrt()).abs() * sig).max().item() <= 1e-5
+        rm2, rv2 = outs["running_mean0"].clone(), outs["running_var0"].clone()
+        ops.bn_stats(out, 1e-5, 0.9, rm2, rv2)      # the stand-alone statistics kernels, which read the activation again
+        em = ((outs["running_mean"] - rm2).abs() / sig.float()).max().item()
+        ev = ((outs["running_var"] - rv2).abs() / v64.float()).max().item()
+        print(f"{name}: running mean {em:.2e}, running var {ev:.2e} (of 1e-5)")
+        assert em <= 1e-5 and ev <= 1e-5, "running buffers"
+
+
+def digests(cases=None):
     """SHA-256 of every output of every case (bitwise comparison of two builds on ONE machine; never committed)"""
     out = {}
-    for name, c in BRANCHES.items():
+    for name, c in (BRANCHES if cases is None else cases).items():
         outs, _ = run_case(name, c)
-        for k in ("out", "dw", "mean", "rstd"):
+        for k in ("out", "dw", "mean", "rstd", "planes", "running_mean", "running_var"):
             if k in outs:
                 out[f"{name}.{k}"] = hashlib.sha256(outs[k].detach().contiguous().cpu().numpy().tobytes()).hexdigest()
     return out

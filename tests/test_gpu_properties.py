@@ -112,7 +112,7 @@ def _check_epilogue_statistics(name, x, p0, p1, y, Cb, Cs, Hs, B, cx, precision=
         _lib.call(name_, ptr(inp), ptr(wq), ops._p(out), *geom, *extra, 1e-5, 0.9, ops._p(mean), ops._p(rstd), ops._p(rm), ops._p(rv),
                   ops._p(ws), nbytes, ops._stream())
         # The epilogue changes no arithmetic of the kernel it runs in.  f32 (conv32.hip) and f16x2 (conv16_f16.hip): the statistics
-        # launch runs the very kernel of the plain launch -- f32_fast_gather / f32_fast_scatter resp. gather16_t / scatter16_t on the
+        # launch runs the very kernel of the plain launch -- conv_gather / conv_scatter (csrc/conv_exec.h) on the
         # same problem type, tile and split rule, the statistics pointer is a kernel argument -- so the outputs must be equal bit for bit.
         # bf16x3, round 3: a plain launch may take ANOTHER kernel than the statistics launch of the same shape -- the pipelined kernel
         # on the v_mfma_f32_16x16x32_bf16 form (launch_plan.h plan_conv: the gather shapes with 256 output columns and 16 K - 64 K rows),

@@ -306,7 +306,7 @@ def test_switches_change_the_routes_they_name(planner):
 # ---- 4. the GPU test's shapes take the branches they are listed for ---------------------------------------------------------------------
 def test_branch_shapes_take_their_branch(planner):
     from tests import test_gpu_launch_plan_branches as T
-    for name, case in T.BRANCHES.items():
+    for name, case in {**T.BRANCHES, **T.VARIANTS}.items():
         got = T.plan_of(planner, case)
         for k, v in case["expect"].items():
             assert got[k] == v, f"{name}: {k} = {got[k]}, listed for {v} ({dict(got)})"

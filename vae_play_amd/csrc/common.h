@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstdarg>
+#include <cstdint>
 #include "../../include/vaeplay_hip.h"
 #include "env.h"
 #include "launch_plan.h"
@@ -51,6 +52,10 @@ inline PlanSwitches plan_switches() {
   if (const char* e = VP_GETENV("VP_WGRAD5_BLOCKS")) sw.wgrad5_blocks = atol(e);
   return sw;
 }
+
+// every pointer is 16-byte aligned (a null pointer counts as aligned)
+template <class... T>
+inline bool aligned16(const T*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
 
 inline unsigned grid_for(size_t work_items, int block, unsigned cap = 256 * 8) {
   size_t g = (work_items + block - 1) / block;

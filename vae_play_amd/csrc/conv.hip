@@ -5,12 +5,6 @@
 #include "conv32.h"
 #include "wgrad5.h"
 
-namespace vp {
-
-static bool aligned16(const void* a, const void* b) { return ((((uintptr_t)a) | ((uintptr_t)b)) & 15) == 0; }
-
-}  // namespace vp
-
 using namespace vp;
 
 extern "C" {
@@ -46,7 +40,7 @@ int vp_conv_gather_f32(const float* big, const float* w_p0, const float* bias, f
   ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
   if (narrow_gather_applicable(g, act)) return narrow_gather_launch(big, w_p0, bias, small_out, g, act, (hipStream_t)stream);
   const ConvPlan pl = plan_conv(false, g, F32, bias != nullptr, act, aligned16(big, w_p0), EPI_NONE, plan_switches());
-  if (pl.route == ROUTE_STAGED) return f32_fast_gather(pl, big, w_p0, bias, small_out, g, act, (hipStream_t)stream);
+  if (pl.route == ROUTE_STAGED) return f32_fast_gather("vp_conv_gather_f32", pl, big, w_p0, bias, small_out, g, act, stream);
   ProbF p = make_probF(big, w_p0, bias, small_out, g, act);
   launch_igemm(p, p.M, p.N, 1, (hipStream_t)stream);
   return check_launch("vp_conv_gather_f32");
@@ -59,7 +53,7 @@ int vp_conv_scatter_f32(const float* small, const float* w_p1, float* big_out, i
   if (rc) return rc;
   ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
   const ConvPlan pl = plan_conv(true, g, F32, false, VP_ACT_NONE, aligned16(small, w_p1), EPI_NONE, plan_switches());
-  if (pl.route == ROUTE_STAGED) return f32_fast_scatter(pl, small, w_p1, big_out, g, (hipStream_t)stream);
+  if (pl.route == ROUTE_STAGED) return f32_fast_scatter("vp_conv_scatter_f32", pl, small, w_p1, big_out, g, stream);
   ProbT p = make_probT(small, w_p1, big_out, g);
   launch_igemm(p, p.M, p.N, stride * stride, (hipStream_t)stream);
   return check_launch("vp_conv_scatter_f32");

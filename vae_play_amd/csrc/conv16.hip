@@ -40,61 +40,10 @@ __global__ void split_pad_kernel(const float* __restrict__ x, u16_t* __restrict_
 //   MODE 1: p1[cb][t][cs] <- w[cs][cb][t]   (one cb, 64 cs per workgroup: 64 x 100-B segments in)
 // SPLIT: write bf16 hi/lo planes (plane stride n) instead of fp32.
 // CsP >= Cs: MODE 1 may zero-pad the small-channel (inner) dimension of p1 to CsP (edge layers on the bf16x3 path).
-template <int MODE, bool SPLIT>
-__global__ void __launch_bounds__(256) pack_w5_tiled_kernel(const float* __restrict__ w, void* __restrict__ outv, int Cs, int Cb,
-                                                            int CsP, int nt, int fmt = SPLIT_BF16) {
-  __shared__ float tile[64][kTaps + 1];
-  const size_t n = (size_t)(MODE == 1 ? CsP : Cs) * Cb * nt;
-  const int fixed = blockIdx.x, j0 = blockIdx.y * 64;
-  const int lim = (MODE == 0 ? Cb : Cs) - j0;           // valid entries of the 64-wide tile
-  const int lim_out = (MODE == 0 ? Cb : CsP) - j0;      // entries written (zeros beyond lim)
-  for (int idx = threadIdx.x; idx < 64 * nt; idx += 256) {
-    const int j = idx / nt, t = idx - j * nt;
-    if (j < lim) {
-      const size_t src = MODE == 0 ? ((size_t)fixed * Cb + j0 + j) * nt + t : ((size_t)(j0 + j) * Cb + fixed) * nt + t;
-      tile[j][t] = w[src];
-    }
-  }
-  __syncthreads();
-  const int inner = MODE == 0 ? Cb : CsP;
-  for (int idx = threadIdx.x; idx < 64 * nt; idx += 256) {
-    const int t = idx >> 6, j = idx & 63;
-    if (j < lim_out) {
-      const size_t o = ((size_t)fixed * nt + t) * inner + j0 + j;
-      const float v = j < lim ? tile[j][t] : 0.f;
-      if constexpr (SPLIT) {
-        u16_t h, l;
-        split_f32(v, h, l, fmt);
-        ((u16_t*)outv)[o] = h;
-        ((u16_t*)outv)[n + o] = l;
-      } else {
-        ((float*)outv)[o] = v;
-      }
-    }
-  }
-}
-
-template <bool SPLIT>
-static int pack_w5_launch(const float* w, void* p0, void* p1, int Cs, int Cb, hipStream_t s, const char* what, int CsP = 0,
-                          int nt = kTaps) {
-  if (CsP < Cs) CsP = Cs;
-  if (p0) hipLaunchKernelGGL((pack_w5_tiled_kernel<0, SPLIT>), dim3(Cs, (Cb + 63) / 64), dim3(256), 0, s, w, p0, Cs, Cb, Cs, nt);
-  if (p1) hipLaunchKernelGGL((pack_w5_tiled_kernel<1, SPLIT>), dim3(Cb, (CsP + 63) / 64), dim3(256), 0, s, w, p1, Cs, Cb, CsP, nt);
-  return check_launch(what);
-}
-
-// ---- all conv weights of a step in ONE launch -------------------------------------------------------------
-// A step re-packs ~10 weight tensors into 1-2 layouts each: 15-20 launches of 7-9 us whose cost is launch latency,
-// not bytes.  The batch kernel walks a job table passed by value: job = (tensor, layout, fp32|split), blockIdx.x
-// is a tile index into the concatenation of all jobs' tiles.
-constexpr int kMaxPackJobs = 32;
-struct PackJob { const float* w; void* out; int Cs, Cb, CsP, mode, split, tile_begin; };
-struct PackTable { PackJob j[kMaxPackJobs]; int n; };
-
+// pack_tile: one 64-wide tile (`fixed`, [j0, j0 + 64)) of one tensor, for the per-tensor kernel and for the batch kernel below.
 template <int MODE, bool SPLIT>
 __device__ __forceinline__ void pack_tile(float (*tile)[kTaps + 1], const float* __restrict__ w, void* __restrict__ outv, int Cs,
-                                          int Cb, int CsP, int fixed, int j0, int fmt) {
-  constexpr int nt = kTaps;
+                                          int Cb, int CsP, int nt, int fixed, int j0, int fmt) {
   const size_t n = (size_t)(MODE == 1 ? CsP : Cs) * Cb * nt;
   const int lim = (MODE == 0 ? Cb : Cs) - j0, lim_out = (MODE == 0 ? Cb : CsP) - j0;
   for (int idx = threadIdx.x; idx < 64 * nt; idx += 256) {
@@ -120,6 +69,30 @@ __device__ __forceinline__ void pack_tile(float (*tile)[kTaps + 1], const float*
   }
 }
 
+template <int MODE, bool SPLIT>
+__global__ void __launch_bounds__(256) pack_w5_tiled_kernel(const float* __restrict__ w, void* __restrict__ outv, int Cs, int Cb,
+                                                            int CsP, int nt, int fmt = SPLIT_BF16) {
+  __shared__ float tile[64][kTaps + 1];
+  pack_tile<MODE, SPLIT>(tile, w, outv, Cs, Cb, CsP, nt, blockIdx.x, blockIdx.y * 64, fmt);
+}
+
+template <bool SPLIT>
+static int pack_w5_launch(const float* w, void* p0, void* p1, int Cs, int Cb, hipStream_t s, const char* what, int CsP = 0,
+                          int nt = kTaps) {
+  if (CsP < Cs) CsP = Cs;
+  if (p0) hipLaunchKernelGGL((pack_w5_tiled_kernel<0, SPLIT>), dim3(Cs, (Cb + 63) / 64), dim3(256), 0, s, w, p0, Cs, Cb, Cs, nt);
+  if (p1) hipLaunchKernelGGL((pack_w5_tiled_kernel<1, SPLIT>), dim3(Cb, (CsP + 63) / 64), dim3(256), 0, s, w, p1, Cs, Cb, CsP, nt);
+  return check_launch(what);
+}
+
+// ---- all conv weights of a step in ONE launch -------------------------------------------------------------
+// A step re-packs ~10 weight tensors into 1-2 layouts each: 15-20 launches of 7-9 us whose cost is launch latency,
+// not bytes.  The batch kernel walks a job table passed by value: job = (tensor, layout, fp32|split), blockIdx.x
+// is a tile index into the concatenation of all jobs' tiles.
+constexpr int kMaxPackJobs = 32;
+struct PackJob { const float* w; void* out; int Cs, Cb, CsP, mode, split, tile_begin; };
+struct PackTable { PackJob j[kMaxPackJobs]; int n; };
+
 __global__ void __launch_bounds__(256) pack_w5_batch_kernel(const PackTable tab) {
   __shared__ float tile[64][kTaps + 1];
   int ji = 0;
@@ -131,12 +104,12 @@ __global__ void __launch_bounds__(256) pack_w5_batch_kernel(const PackTable tab)
   const int fixed = tl / ntile, j0 = (tl - fixed * ntile) * 64;
   if (jb.mode == 0) {
     const int fmt = jb.split == 2 ? SPLIT_F16 : SPLIT_BF16;       // vp_pack_job.split: 0 fp32 | 1 bf16 pair | 2 fp16 pair
-    if (jb.split) pack_tile<0, true>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, fixed, j0, fmt);
-    else pack_tile<0, false>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, fixed, j0, fmt);
+    if (jb.split) pack_tile<0, true>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, kTaps, fixed, j0, fmt);
+    else pack_tile<0, false>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, kTaps, fixed, j0, fmt);
   } else {
     const int fmt = jb.split == 2 ? SPLIT_F16 : SPLIT_BF16;
-    if (jb.split) pack_tile<1, true>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, fixed, j0, fmt);
-    else pack_tile<1, false>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, fixed, j0, fmt);
+    if (jb.split) pack_tile<1, true>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, kTaps, fixed, j0, fmt);
+    else pack_tile<1, false>(tile, jb.w, jb.out, jb.Cs, jb.Cb, jb.CsP, kTaps, fixed, j0, fmt);
   }
 }
 
@@ -232,6 +205,54 @@ __global__ void unpack_dw_im2col5_kernel(const float* __restrict__ dwc, float* _
   }
 }
 
+// ---- finaliser of the BatchNorm statistics that a convolution epilogue emits (conv_exec.h: conv5_stats), for every arithmetic ------
+// one 256-thread workgroup per channel; groups are shifted to the pivot of group 0 and summed in fp64:
+//   sum(x - P) = s_g + n_g d,  sum((x - P)^2) = q_g + 2 d s_g + n_g d^2,  d = p_g - P
+__global__ void __launch_bounds__(256) bn_stats_slab_final_kernel(const float* __restrict__ slab, int G, int tiles_m, int BM, long M, long R,
+                                                                  int C, float eps, float momentum, float* __restrict__ mean,
+                                                                  float* __restrict__ rstd, float* __restrict__ rm, float* __restrict__ rv) {
+  __shared__ double shs[4], shq[4];
+  const int c = blockIdx.x;
+  const float* pv = slab + ((size_t)0 * C + c) * G;
+  const float* sv = slab + ((size_t)1 * C + c) * G;
+  const float* qv = slab + ((size_t)2 * C + c) * G;
+  const double P = (double)pv[0];
+  double S = 0.0, Q = 0.0;
+  for (int g = threadIdx.x; g < G; g += 256) {
+    const int tile = g % tiles_m;
+    const long left = M - (long)tile * BM;
+    const double n = (double)(left < BM ? left : BM);
+    const double d = (double)pv[g] - P, s = (double)sv[g], q = (double)qv[g];
+    S += s + n * d;
+    Q += q + 2.0 * d * s + n * d * d;
+  }
+  S = wave_sum_d(S);
+  Q = wave_sum_d(Q);
+  if ((threadIdx.x & 63) == 0) { shs[threadIdx.x >> 6] = S; shq[threadIdx.x >> 6] = Q; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  S = (shs[0] + shs[1]) + (shs[2] + shs[3]);
+  Q = (shq[0] + shq[1]) + (shq[2] + shq[3]);
+  const double ms = S / (double)R;
+  double var = Q / (double)R - ms * ms;
+  if (var < 0.0) var = 0.0;
+  const double m = P + ms;
+  mean[c] = (float)m;
+  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
+  if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)m;
+  if (rv) {
+    const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
+    rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
+  }
+}
+
+// the slab geometry is the launch's plan
+int stats_finish(const ConvPlan& pl, const StatOut& o, hipStream_t stream, const char* what) {
+  hipLaunchKernelGGL(bn_stats_slab_final_kernel, dim3((unsigned)pl.N), dim3(256), 0, stream, (const float*)o.ws, pl.stat_tiles_m * pl.gz,
+                     pl.stat_tiles_m, pl.bm, pl.M, pl.stat_R, (int)pl.N, o.eps, o.momentum, o.mean, o.rstd, o.running_mean, o.running_var);
+  return check_launch(what);
+}
+
 }  // namespace vp
 
 using namespace vp;
@@ -294,33 +315,29 @@ int vp_pack_w5_p1_split_padded(const float* w_ref, void* p1_split, int Csmall, i
   return pack_w5_launch<true>(w_ref, nullptr, p1_split, Csmall, Cbig, (hipStream_t)stream, "vp_pack_w5_p1_split_padded", Csmall_pad);
 }
 
-
-
 int vp_conv5_gather_bf16x3(const void* big_split, const void* w_p0_split, const float* bias, float* small_out, int B, int Hs,
                            int Ws, int Cbig, int Csmall, int stride, int act, vp_stream stream) {
-  return gather16<0>(big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, act, stream);
+  return gather16<0>("vp_conv5_gather_bf16x3", big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, act, stream);
 }
 
 int vp_conv_gather_bf16x3(const void* big_split, const void* w_p0_split, const float* bias, float* small_out, int B, int Hs, int Ws,
                           int Hb, int Wb, int Cbig, int Csmall, int ks, int stride, int act, vp_stream stream) {
-  return gather16<0>(big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, act, stream);
+  return gather16<0>("vp_conv_gather_bf16x3", big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, act, stream);
 }
-
-
 
 int vp_conv5_scatter_bf16x3(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
                             int Cbig, int stride, vp_stream stream) {
-  return scatter16<0>(small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride, stream);
+  return scatter16<0>("vp_conv5_scatter_bf16x3", small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride, stream);
 }
 
 int vp_conv_scatter_bf16x3(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Hb, int Wb,
                            int Csmall, int Cbig, int ks, int stride, vp_stream stream) {
-  return scatter16<0>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream);
+  return scatter16<0>("vp_conv_scatter_bf16x3", small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream);
 }
 
 int vp_conv_scatter_bias_bf16x3(const void* small_split, const void* w_p1_split, const float* bias, float* big_out, int B, int Hs, int Ws,
                                 int Hb, int Wb, int Csmall, int Cbig, int ks, int stride, vp_stream stream) {
-  return scatter16<0>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream, 1.f, bias);
+  return scatter16<0>("vp_conv_scatter_bias_bf16x3", small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream, 1.f, bias);
 }
 
 int vp_pack_w_split(const float* w_ref, void* p0_split, void* p1_split, int Csmall, int Cbig, int ks, vp_stream stream) {
@@ -341,113 +358,38 @@ size_t vp_conv_wgrad_bf16x3_workspace_bytes(int B, int Hs, int Ws, int Hb, int W
 
 int vp_conv5_wgrad_bf16x3(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Cbig,
                           int Csmall, int stride, void* ws, size_t ws_bytes, vp_stream stream) {
-  return wgrad16<0>(big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws, ws_bytes, stream);
+  return wgrad16<0>("vp_conv5_wgrad_bf16x3", big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws, ws_bytes, stream);
 }
 
 int vp_conv5_wgrad_bf16x3_cus(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Cbig,
                               int Csmall, int stride, int max_cus, void* ws, size_t ws_bytes, vp_stream stream) {
-  return wgrad16<0>(big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws, ws_bytes, stream, 1.f, max_cus);
+  return wgrad16<0>("vp_conv5_wgrad_bf16x3_cus", big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws, ws_bytes, stream, 1.f, max_cus);
 }
 
 int vp_conv_wgrad_bf16x3(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Hb, int Wb, int Cbig,
                          int Csmall, int ks, int stride, void* ws, size_t ws_bytes, vp_stream stream) {
-  return wgrad16<0>(big_split, small_split, dw_ref, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, ws, ws_bytes, stream);
+  return wgrad16<0>("vp_conv_wgrad_bf16x3", big_split, small_split, dw_ref, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, ws, ws_bytes, stream);
 }
-
-
-
-}
-
-
-namespace vp {
-// one 256-thread workgroup per channel; groups are shifted to the pivot of group 0 and summed in fp64:
-//   sum(x - P) = s_g + n_g d,  sum((x - P)^2) = q_g + 2 d s_g + n_g d^2,  d = p_g - P
-__global__ void __launch_bounds__(256) bn_stats_slab_final_kernel(const float* __restrict__ slab, int G, int tiles_m, int BM, long M, long R,
-                                                                  int C, float eps, float momentum, float* __restrict__ mean,
-                                                                  float* __restrict__ rstd, float* __restrict__ rm, float* __restrict__ rv) {
-  __shared__ double shs[4], shq[4];
-  const int c = blockIdx.x;
-  const float* pv = slab + ((size_t)0 * C + c) * G;
-  const float* sv = slab + ((size_t)1 * C + c) * G;
-  const float* qv = slab + ((size_t)2 * C + c) * G;
-  const double P = (double)pv[0];
-  double S = 0.0, Q = 0.0;
-  for (int g = threadIdx.x; g < G; g += 256) {
-    const int tile = g % tiles_m;
-    const long left = M - (long)tile * BM;
-    const double n = (double)(left < BM ? left : BM);
-    const double d = (double)pv[g] - P, s = (double)sv[g], q = (double)qv[g];
-    S += s + n * d;
-    Q += q + 2.0 * d * s + n * d * d;
-  }
-  S = wave_sum_d(S);
-  Q = wave_sum_d(Q);
-  if ((threadIdx.x & 63) == 0) { shs[threadIdx.x >> 6] = S; shq[threadIdx.x >> 6] = Q; }
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  S = (shs[0] + shs[1]) + (shs[2] + shs[3]);
-  Q = (shq[0] + shq[1]) + (shq[2] + shq[3]);
-  const double ms = S / (double)R;
-  double var = Q / (double)R - ms * ms;
-  if (var < 0.0) var = 0.0;
-  const double m = P + ms;
-  mean[c] = (float)m;
-  rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
-  if (rm) rm[c] = (1.f - momentum) * rm[c] + momentum * (float)m;
-  if (rv) {
-    const double unb = R > 1 ? var * (double)R / (double)(R - 1) : var;
-    rv[c] = (1.f - momentum) * rv[c] + momentum * (float)unb;
-  }
-}
-}  // namespace vp
-
-extern "C" {
 
 size_t vp_conv5_stats_workspace_bytes(int family, int B, int Hs, int Ws, int Cbig, int Csmall, int stride) {
   return plan_stats(family, BF16X3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches()).stat_floats * sizeof(float);
 }
 
-}
-namespace vp {
-// the finaliser for every arithmetic: the slab geometry is the launch's plan
-int stats_finish(const ConvPlan& pl, const float* slab, float eps, float momentum, float* mean, float* rstd, float* rm, float* rv, hipStream_t stream,
-                 const char* what) {
-  hipLaunchKernelGGL(bn_stats_slab_final_kernel, dim3((unsigned)pl.N), dim3(256), 0, stream, slab, pl.stat_tiles_m * pl.gz, pl.stat_tiles_m, pl.bm,
-                     pl.M, pl.stat_R, (int)pl.N, eps, momentum, mean, rstd, rm, rv);
-  return check_launch(what);
-}
-}  // namespace vp
-extern "C" {
-
 int vp_conv5_gather_stats_bf16x3(const void* big_split, const void* w_p0_split, float* small_out, int B, int Hs, int Ws, int Cbig,
                                  int Csmall, int stride, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                                  float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
-  VP_REQUIRE(big_split && w_p0_split && small_out && mean && rstd && ws, "vp_conv5_gather_stats_bf16x3: null pointer");
-  const ConvPlan pl = plan_stats(0, BF16X3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
-  VP_REQUIRE(pl.stat_ok, "vp_conv5_gather_stats_bf16x3: this shape cannot emit statistics (vp_conv5_stats_workspace_bytes() == 0)");
-  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_gather_stats_bf16x3: workspace too small");
-  int rc = gather16_t<ProbF16>(pl, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), big_split, w_p0_split, nullptr, small_out, VP_ACT_NONE, stream,
-                               (float*)ws);
-  if (rc) return rc;
-  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
+  return conv5_stats("vp_conv5_gather_stats_bf16x3", "vp_conv5_stats_workspace_bytes", conv_gather<ProbF16, FORMS_ALL, TILES_ALL>, 0, BF16X3, true,
+                     big_split, w_p0_split, small_out, B, Hs, Ws, Cbig, Csmall, stride,
+                     {eps, momentum, mean, rstd, running_mean, running_var, ws, ws_bytes}, stream);
 }
 
 int vp_conv5_scatter_stats_bf16x3(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
                                   int Cbig, int stride, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                                   float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
-  VP_REQUIRE(small_split && w_p1_split && big_out && mean && rstd && ws, "vp_conv5_scatter_stats_bf16x3: null pointer");
-  const ConvPlan pl = plan_stats(1, BF16X3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
-  VP_REQUIRE(pl.stat_ok, "vp_conv5_scatter_stats_bf16x3: this shape cannot emit statistics (vp_conv5_stats_workspace_bytes() == 0)");
-  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_scatter_stats_bf16x3: workspace too small");
-  int rc = scatter16_t<ProbT16>(pl, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), small_split, w_p1_split, big_out, stream, (float*)ws);
-  if (rc) return rc;
-  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
+  return conv5_stats("vp_conv5_scatter_stats_bf16x3", "vp_conv5_stats_workspace_bytes", conv_scatter<ProbT16, FORMS_ALL, TILES_ALL>, 1, BF16X3, true,
+                     small_split, w_p1_split, big_out, B, Hs, Ws, Cbig, Csmall, stride,
+                     {eps, momentum, mean, rstd, running_mean, running_var, ws, ws_bytes}, stream);
 }
-
-
-}
-
-extern "C" {
 
 int vp_im2col5s2_cols(int C) { return im2col5_kc(C); }
 

@@ -3,7 +3,13 @@
 #define VP_PCFG_LIBRARY 1
 #include "conv16_impl.h"
 
-#define VP_PRODUCTS_OK(what) VP_REQUIRE(products == 2 || products == 3, what ": products must be 2 or 3")
+// checks `products` and hands it to f as a compile-time constant (std::integral_constant<int, 2 | 3>)
+template <class F>
+static int with_products(const char* what, int products, F f) {
+  VP_REQUIRE(products == 2 || products == 3, "%s: products must be 2 or 3", what);
+  return products == 2 ? f(std::integral_constant<int, 2>()) : f(std::integral_constant<int, 3>());
+}
+#define VP_PRODUCTS(what, call) with_products(what, products, [&](auto pr) { constexpr int PR = decltype(pr)::value; return call; })
 
 extern "C" {
 
@@ -14,43 +20,42 @@ extern "C" {
 // of a gradient operand applied; 1 for activations and weights).
 int vp_conv5_gather_f16(const void* big_split, const void* w_p0_split, const float* bias, float* small_out, int B, int Hs,
                         int Ws, int Cbig, int Csmall, int stride, int act, int products, float out_scale, vp_stream stream) {
-  VP_PRODUCTS_OK("vp_conv5_gather_f16");
-  return products == 2 ? gather16<2>(big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, act, stream, out_scale)
-                       : gather16<3>(big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, act, stream, out_scale);
+  return VP_PRODUCTS("vp_conv5_gather_f16", gather16<PR>("vp_conv5_gather_f16", big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hs * stride,
+                                                         Ws * stride, Cbig, Csmall, 5, stride, act, stream, out_scale));
 }
 int vp_conv_gather_f16(const void* big_split, const void* w_p0_split, const float* bias, float* small_out, int B, int Hs, int Ws,
                        int Hb, int Wb, int Cbig, int Csmall, int ks, int stride, int act, int products, float out_scale, vp_stream stream) {
-  VP_PRODUCTS_OK("vp_conv_gather_f16");
-  return products == 2 ? gather16<2>(big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, act, stream, out_scale)
-                       : gather16<3>(big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, act, stream, out_scale);
+  return VP_PRODUCTS("vp_conv_gather_f16", gather16<PR>("vp_conv_gather_f16", big_split, w_p0_split, bias, small_out, B, Hs, Ws, Hb, Wb, Cbig,
+                                                        Csmall, ks, stride, act, stream, out_scale));
 }
 int vp_conv5_scatter_f16(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
                          int Cbig, int stride, int products, float out_scale, vp_stream stream) {
-  VP_PRODUCTS_OK("vp_conv5_scatter_f16");
-  return products == 2 ? scatter16<2>(small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride, stream, out_scale)
-                       : scatter16<3>(small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride, Ws * stride, Csmall, Cbig, 5, stride, stream, out_scale);
+  return VP_PRODUCTS("vp_conv5_scatter_f16", scatter16<PR>("vp_conv5_scatter_f16", small_split, w_p1_split, big_out, B, Hs, Ws, Hs * stride,
+                                                           Ws * stride, Csmall, Cbig, 5, stride, stream, out_scale));
 }
 int vp_conv_scatter_f16(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Hb, int Wb,
                         int Csmall, int Cbig, int ks, int stride, int products, float out_scale, vp_stream stream) {
-  VP_PRODUCTS_OK("vp_conv_scatter_f16");
-  return products == 2 ? scatter16<2>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream, out_scale)
-                       : scatter16<3>(small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall, Cbig, ks, stride, stream, out_scale);
+  return VP_PRODUCTS("vp_conv_scatter_f16", scatter16<PR>("vp_conv_scatter_f16", small_split, w_p1_split, big_out, B, Hs, Ws, Hb, Wb, Csmall,
+                                                          Cbig, ks, stride, stream, out_scale));
 }
 int vp_conv5_wgrad_f16x2(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Cbig,
                          int Csmall, int stride, float out_scale, void* ws, size_t ws_bytes, vp_stream stream) {
-  return wgrad16<2>(big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws, ws_bytes, stream, out_scale);
+  return wgrad16<2>("vp_conv5_wgrad_f16x2", big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws,
+                    ws_bytes, stream, out_scale);
 }
 int vp_conv5_wgrad_f16x2_cus(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Cbig,
                              int Csmall, int stride, float out_scale, int max_cus, void* ws, size_t ws_bytes, vp_stream stream) {
-  return wgrad16<2>(big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws, ws_bytes, stream, out_scale, max_cus);
+  return wgrad16<2>("vp_conv5_wgrad_f16x2_cus", big_split, small_split, dw_ref, B, Hs, Ws, Hs * stride, Ws * stride, Cbig, Csmall, 5, stride, ws,
+                    ws_bytes, stream, out_scale, max_cus);
 }
 
 int vp_conv_wgrad_f16x2(const void* big_split, const void* small_split, float* dw_ref, int B, int Hs, int Ws, int Hb, int Wb, int Cbig,
                         int Csmall, int ks, int stride, float out_scale, void* ws, size_t ws_bytes, vp_stream stream) {
-  return wgrad16<2>(big_split, small_split, dw_ref, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, ws, ws_bytes, stream, out_scale);
+  return wgrad16<2>("vp_conv_wgrad_f16x2", big_split, small_split, dw_ref, B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride, ws, ws_bytes, stream,
+                    out_scale);
 }
 
-// the same on fp16-pair planes (forward layers: out_scale is 1)
+// BatchNorm statistics from the epilogue on fp16-pair planes (forward layers: out_scale is 1); descriptor mode = products - 1
 size_t vp_conv5_stats_f16_workspace_bytes(int family, int B, int Hs, int Ws, int Cbig, int Csmall, int stride) {
   return plan_stats(family, F16_2, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches()).stat_floats * sizeof(float);
 }
@@ -58,31 +63,19 @@ size_t vp_conv5_stats_f16_workspace_bytes(int family, int B, int Hs, int Ws, int
 int vp_conv5_gather_stats_f16(const void* big_split, const void* w_p0_split, float* small_out, int B, int Hs, int Ws, int Cbig,
                               int Csmall, int stride, int products, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                               float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
-  VP_REQUIRE(products == 2 || products == 3, "vp_conv5_gather_stats_f16: products must be 2 or 3");
-  VP_REQUIRE(big_split && w_p0_split && small_out && mean && rstd && ws, "vp_conv5_gather_stats_f16: null pointer");
-  const ConvPlan pl = plan_stats(0, products == 2 ? F16_2 : F16_3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
-  VP_REQUIRE(pl.stat_ok, "vp_conv5_gather_stats_f16: this shape cannot emit statistics (vp_conv5_stats_f16_workspace_bytes() == 0)");
-  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_gather_stats_f16: workspace too small");
-  const ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5);
-  int rc = products == 2 ? gather16_t<ProbF16X>(pl, g, big_split, w_p0_split, nullptr, small_out, VP_ACT_NONE, stream, (float*)ws)
-                         : gather16_t<ProbF16H>(pl, g, big_split, w_p0_split, nullptr, small_out, VP_ACT_NONE, stream, (float*)ws);
-  if (rc) return rc;
-  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
+  return VP_PRODUCTS("vp_conv5_gather_stats_f16",
+                     conv5_stats("vp_conv5_gather_stats_f16", "vp_conv5_stats_f16_workspace_bytes", conv_gather<ProbF16T<true, PR - 1>, FORMS_ALL, TILES_ALL>,
+                                 0, arith16<PR>(), true, big_split, w_p0_split, small_out, B, Hs, Ws, Cbig, Csmall, stride,
+                                 {eps, momentum, mean, rstd, running_mean, running_var, ws, ws_bytes}, stream));
 }
 
 int vp_conv5_scatter_stats_f16(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
                                int Cbig, int stride, int products, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                                float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
-  VP_REQUIRE(products == 2 || products == 3, "vp_conv5_scatter_stats_f16: products must be 2 or 3");
-  VP_REQUIRE(small_split && w_p1_split && big_out && mean && rstd && ws, "vp_conv5_scatter_stats_f16: null pointer");
-  const ConvPlan pl = plan_stats(1, products == 2 ? F16_2 : F16_3, B, Hs, Ws, Cbig, Csmall, stride, true, plan_switches());
-  VP_REQUIRE(pl.stat_ok, "vp_conv5_scatter_stats_f16: this shape cannot emit statistics (vp_conv5_stats_f16_workspace_bytes() == 0)");
-  if (ws_bytes < pl.stat_floats * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_conv5_scatter_stats_f16: workspace too small");
-  const ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5);
-  int rc = products == 2 ? scatter16_t<ProbT16X>(pl, g, small_split, w_p1_split, big_out, stream, (float*)ws)
-                         : scatter16_t<ProbT16H>(pl, g, small_split, w_p1_split, big_out, stream, (float*)ws);
-  if (rc) return rc;
-  return stats_finish(pl, (const float*)ws, eps, momentum, mean, rstd, running_mean, running_var, (hipStream_t)stream, "vp_conv5_*_stats_bf16x3(final)");
+  return VP_PRODUCTS("vp_conv5_scatter_stats_f16",
+                     conv5_stats("vp_conv5_scatter_stats_f16", "vp_conv5_stats_f16_workspace_bytes", conv_scatter<ProbT16T<true, PR - 1>, FORMS_ALL, TILES_ALL>,
+                                 1, arith16<PR>(), true, small_split, w_p1_split, big_out, B, Hs, Ws, Cbig, Csmall, stride,
+                                 {eps, momentum, mean, rstd, running_mean, running_var, ws, ws_bytes}, stream));
 }
 
 }

@@ -424,6 +424,9 @@ int vp_add_f32(const float* a, const float* b, float* out, size_t n, vp_stream s
  * relative per layer, used for the backward layers (gradients).  fp16's range is narrow (|x| <= 65504, 2^-24 absolute step below
  * 2^-14), so a producer of GRADIENT planes multiplies by a power of two (`scale`) and the consuming launch multiplies its
  * accumulators by out_scale = 1/scale; activations and weights use scale 1 (values saturate at +-65504 instead of overflowing).
+ * `products` = 1 (gather / scatter entry points only; fused inference, precision "f16"): ah*bh, ONE MFMA per fragment pair -- only the hi
+ * plane of either operand is fetched (11 significant bits each; the lo planes of the buffers are never read and may be left unwritten).
+ * Replaces models/networks.py:14,38 in eval mode, where activations behind a folded BatchNorm + ReLU are O(1); no gradient form.
  * Split formats: 0 = bf16 pair (the *_bf16x3 entry points), 1 = fp16 pair (the *_f16* entry points); same buffer sizes.
  * Every *_fmt producer with format 0 and scale 1 is bit-identical to the entry point without the suffix. */
 #define VP_SPLIT_BF16 0
@@ -446,8 +449,9 @@ int vp_bn_act_bwd_split_fmt_sat_f32(const float* x, const float* dy, const float
                                     void* ws, size_t ws_bytes, vp_stream stream);
 int vp_im2col5s2_split_fmt_f32(const float* x, void* out_split, int B, int C, int Hb, int Wb, int nchw, int fmt, vp_stream stream);
 int vp_pack_w_im2col5_split_fmt(const float* w_ref, void* out_split, int Cout, int C, int fmt, vp_stream stream);
-/* the three families; arguments as the *_bf16x3 entry points plus products (2 | 3) and out_scale (workspace queries of the weight
- * gradient: the *_bf16x3 ones).  The weight gradient exists in the two-product form only. */
+/* the three families; arguments as the *_bf16x3 entry points plus products (1 | 2 | 3) and out_scale (workspace queries of the weight
+ * gradient: the *_bf16x3 ones).  The weight gradient exists in the two-product form only; the *_stats_* entry points take
+ * products 2 | 3 and return VP_ERR_ARG for 1. */
 int vp_conv5_gather_f16(const void* big_split, const void* w_p0_split, const float* bias, float* small_out,
                         int B, int Hs, int Ws, int Cbig, int Csmall, int stride, int act, int products, float out_scale, vp_stream stream);
 int vp_conv_gather_f16(const void* big_split, const void* w_p0_split, const float* bias, float* small_out, int B, int Hs, int Ws,
@@ -487,7 +491,7 @@ int vp_bn_fold_f32(const float* gamma, const float* beta, const float* running_m
  * models/networks.py:27-29 and :43-45 in eval mode): v = act(fma(acc, scale[n], shift[n])), act none | relu, written as fp32 NHWC
  * (out_f32) and / or as the split planes of the next layer's operand (out_split, bf16x3 only: hi plane, then lo plane, the layout
  * and rounding of vp_bn_act_fwd_split_f32); at least one output, 16-byte aligned.  The f32 entry points take out_split == NULL only.
- * vp_conv5_affine_supported(family 0 gather | 1 scatter, precision 0 bf16x3 | 1 f32, ...) == 0: this launch shape does not fuse (its
+ * vp_conv5_affine_supported(family 0 gather | 1 scatter, precision 0 bf16x3 | 1 f32 | 2 one-product f16, ...) == 0: this launch shape does not fuse (its
  * plain launch splits K, or its channel counts are outside the instantiated tiles: contracted side a multiple of 64 [f32: 32],
  * output side >= 64 and a multiple of 8): use the plain entry point + vp_bn_act_fwd_split_f32. */
 int vp_conv5_affine_supported(int family, int precision, int B, int Hs, int Ws, int Cbig, int Csmall, int stride);
@@ -499,6 +503,18 @@ int vp_conv5_gather_affine_f32(const float* big, const float* w_p0, const float*
                                int B, int Hs, int Ws, int Cbig, int Csmall, int stride, int act, vp_stream stream);
 int vp_conv5_scatter_affine_f32(const float* small, const float* w_p1, const float* scale, const float* shift, float* out_f32, void* out_split,
                                 int B, int Hs, int Ws, int Csmall, int Cbig, int stride, int act, vp_stream stream);
+/* The same block in one-product fp16 (precision code 2 of vp_conv5_affine_supported; the same shape rules as bf16x3): replaces
+ * models/networks.py:14,38 with :27-29 / :43-45 in eval mode.  Operands are fp16 planes (format 1) of which only the hi planes are read,
+ * contraction as products = 1 above, v = act(fma(acc, scale[n], shift[n])).  out_split is written according to out_fmt:
+ *   0  bf16 pair, both planes (exactly the bf16x3 entry point's write: the consumer is a bf16x3 kernel)
+ *   1  fp16 pair, both planes (vp_split_fmt_f32's rounding, saturating at +-65504)
+ *   2  the fp16 hi plane only; the lo plane of the buffer is NOT written (the consumer is a one-product layer). */
+int vp_conv5_gather_affine_f16(const void* big_split, const void* w_p0_split, const float* scale, const float* shift, float* out_f32,
+                               void* out_split, int B, int Hs, int Ws, int Cbig, int Csmall, int stride, int act, int out_fmt,
+                               vp_stream stream);
+int vp_conv5_scatter_affine_f16(const void* small_split, const void* w_p1_split, const float* scale, const float* shift, float* out_f32,
+                                void* out_split, int B, int Hs, int Ws, int Csmall, int Cbig, int stride, int act, int out_fmt,
+                                vp_stream stream);
 
 /* ---- SCSEBlock (models/blocks.py:52-65), fp32 NHWC, forward and backward ------------------------------------------------------
  * y[b,p,ch] = x (c[b,ch] + s[b,p]) with the channel gate c = sigmoid(W2 relu(W1 mean_p(x) + b1) + b2) (W1 [C/r][C], W2 [C][C/r], the

@@ -17,7 +17,14 @@ images/s of ``FusedVAEInference.score`` with 1 and K draws per image (eager and 
 in eval mode, then per-image BCE, density ratio and log-sum-exp in ATen (key ``score``; the other keys are unchanged).  The result
 is one JSON document (``--out``).
 
+With ``f16`` among ``--precisions`` (the one-product fp16 plans, which have no module path to stand against) the tool adds the
+key ``modes``: per shape, ``reconstruct`` -- and with ``--score K`` also ``score`` with K draws -- of the plans of
+every named precision over ONE model, eager and replayed, alternating in the same windows; per variant the median, min, max and the
+spread max - min over the windows, and whether f16 beats bf16x3 by more than the sum of both spreads.  ``--layers`` then also lists
+every 5x5 stride-2 layer's launch in f16 next to bf16x3 (key ``layers_f16``).  The module-path legs run for bf16x3 and f32 as before.
+
     python tools/bench_infer.py --out bench_out/infer.json
+    python tools/bench_infer.py --precisions f16,bf16x3,f32 --layers --score 8 --out bench_out/infer_f16.json
     python tools/bench_infer.py --score 8 --score-only --out bench_out/infer_score.json
 """
 import argparse
@@ -228,6 +235,123 @@ def bench_layers(C, S, z, B, prec, args):
     return res
 
 
+def _with_spread(r, B, key):
+    for v in r.values():
+        v["spread_ms"] = v["max"] - v["min"]
+        v[key] = B / (v["ms"] * 1e-3)
+    return r
+
+
+def _f16_verdict(r, suffix):
+    """is f16 faster than bf16x3 by more than the sum of both variants' window-to-window spreads?"""
+    f, b = r.get("f16" + suffix), r.get("bf16x3" + suffix)
+    if f is None or b is None:
+        return None
+    return {"saved_ms": b["ms"] - f["ms"], "sum_of_spreads_ms": f["spread_ms"] + b["spread_ms"], "speedup": b["ms"] / f["ms"],
+            "faster_by_more_than_spreads": bool(b["ms"] - f["ms"] > f["spread_ms"] + b["spread_ms"])}
+
+
+def bench_modes(name, C, S, z, B, precs, args, score_k=0):
+    """the plans of ``precs`` over one model in alternating windows: reconstruct, and score with ``score_k`` draws"""
+    import vae_play_amd as V
+    torch.manual_seed(0)
+    vae = V.VAE(S, z, C).cuda().eval()
+    randomise_bn(vae, 1)
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand((B, C, S, S), generator=g).cuda()
+    eps = torch.randn((B, z), generator=g).cuda()
+    eager = {p: V.FusedVAEInference(vae, B, S, C, precision=p) for p in precs}
+    graph = {p: V.FusedVAEInference(vae, B, S, C, precision=p) for p in precs}
+    out = {}
+    if score_k:
+        eps_k = torch.randn((B, score_k, z), generator=g).cuda()
+        for p in precs:
+            graph[p].score(x, score_k, eps_k)
+    for p in precs:
+        graph[p].capture()
+    base = eager[precs[-1]].reconstruct(x, eps)[0]      # (recorded, not asserted: the parity tests assert)
+    out["max_abs_diff_x_tilde_vs_" + precs[-1]] = {p: (eager[p].reconstruct(x, eps)[0] - base).abs().max().item() for p in precs}
+    variants = {}
+    for p in precs:
+        variants[p] = (lambda q: lambda: eager[q].reconstruct(x, eps))(p)
+        variants[p + "_graph"] = (lambda q: lambda: graph[q].reconstruct(x, eps))(p)
+    r = _with_spread(ab(variants, args.iters, args.reps, args.warmup), B, "images_per_s")
+    out["reconstruct"] = r
+    out["reconstruct_f16_vs_bf16x3"] = {"eager": _f16_verdict(r, ""), "graph": _f16_verdict(r, "_graph")}
+    for k, v in r.items():
+        print(f"{name} modes reconstruct {k}: {v['ms']:.3f} ms [{v['min']:.3f}, {v['max']:.3f}]  {v['images_per_s']:.0f} images/s", flush=True)
+    print(f"{name} modes reconstruct f16 vs bf16x3: {out['reconstruct_f16_vs_bf16x3']}", flush=True)
+    if score_k:
+        variants = {}
+        for p in precs:
+            variants[p] = (lambda q: lambda: eager[q].score(x, score_k, eps_k))(p)
+            variants[p + "_graph"] = (lambda q: lambda: graph[q].score(x, score_k, eps_k))(p)
+        r = _with_spread(ab(variants, args.iters, args.reps, args.warmup), B, "scored_images_per_s")
+        out[f"score_k{score_k}"] = r
+        out[f"score_k{score_k}_f16_vs_bf16x3"] = {"eager": _f16_verdict(r, ""), "graph": _f16_verdict(r, "_graph")}
+        for k, v in r.items():
+            print(f"{name} modes score k={score_k} {k}: {v['ms']:.3f} ms [{v['min']:.3f}, {v['max']:.3f}]  {v['scored_images_per_s']:.0f} images/s",
+                  flush=True)
+    return out
+
+
+def bench_layers_f16(C, S, z, B, args):
+    """every 5x5 stride-2 layer of the shape as the f16 plan launches it next to the bf16x3 plan's launch: the fused launch where the
+    shape fuses (f16 writes the hi plane, bf16x3 both planes; fp32 for the layers whose consumer reads fp32), else the plain
+    convolution (the normalise pass that follows is the same kernel in both plans)"""
+    import vae_play_amd as V
+    from vae_play_amd import _lib, ops
+    from ctypes import c_void_p
+    lib = _lib.load()
+    vae = V.VAE(S, z, C)
+    L = vae.iter_level
+    enc_ch = [C] + [blk.conv.weight.shape[0] for blk in vae.encoder.conv]
+    dec_ch = [vae.decoder._c0] + [blk.conv.weight.shape[1] for blk in list(vae.decoder.conv)[:L]]
+    layers = [(f"enc{i}", 0, S >> (i + 1), enc_ch[i], enc_ch[i + 1]) for i in range(1, L)]
+    layers += [(f"dec{i}", 1, 8 << i, dec_ch[i], dec_ch[i + 1]) for i in range(L)]
+    res = {}
+    P = lambda t: None if t is None else c_void_p(t.data_ptr())      # noqa: E731
+    for tag, fam, Hs, Cin, Cout in layers:
+        Cbig, Csmall = (Cin, Cout) if fam == 0 else (Cout, Cin)
+        fusable = ops.conv5_affine_supported(fam, "f16", B, Hs, Hs, Cbig, Csmall, 2)
+        Hin, Ho = (2 * Hs, Hs) if fam == 0 else (Hs, 2 * Hs)
+        a = torch.randn((B, Cin, Hin, Hin), device="cuda").contiguous(memory_format=torch.channels_last)
+        w = torch.randn((Cout, Cin, 5, 5) if fam == 0 else (Cin, Cout, 5, 5), device="cuda") / (25 * Cin) ** 0.5
+        n_out = B * Ho * Ho * Cout
+        last = tag in (f"dec{L - 1}", f"enc{L - 1}")      # consumers that read fp32
+        y = torch.empty(n_out, device="cuda")
+        ys = None if last else ops.empty_split(n_out, a)
+        ones, zeros = torch.ones(Cout, device="cuda"), torch.zeros(Cout, device="cuda")
+        s = c_void_p(torch.cuda.current_stream().cuda_stream)
+        geom = (B, Hs, Hs, Cin, Cout, 2)
+        ab16, wb16 = ops.split_f32(a), ops.pack_w5_split(w, fam == 0, fam == 1)[fam]
+        ah16, wh16 = ops.split_f32(a, ops.SPLIT_F16), ops.pack_w5_split(w, fam == 0, fam == 1, ops.SPLIT_F16)[fam]
+        fam_name = ("gather", "scatter")[fam]
+        yo = None if ys is not None else P(y)
+        if fusable:
+            fn_h, fn_b = getattr(lib, f"vp_conv5_{fam_name}_affine_f16"), getattr(lib, f"vp_conv5_{fam_name}_affine_bf16x3")
+            fmt = ops.OUT_BF16_PAIR if tag == f"dec{L - 1}" else ops.OUT_F16_HI
+            variants = {"f16": lambda: _lib.check(fn_h(P(ah16), P(wh16), P(ones), P(zeros), yo, P(ys), *geom, ops.ACT_RELU, fmt, s)),
+                        "bf16x3": lambda: _lib.check(fn_b(P(ab16), P(wb16), P(ones), P(zeros), yo, P(ys), *geom, ops.ACT_RELU, s))}
+        else:
+            fn_h, fn_b = getattr(lib, f"vp_conv5_{fam_name}_f16"), getattr(lib, f"vp_conv5_{fam_name}_bf16x3")
+            if fam == 0:
+                variants = {"f16": lambda: _lib.check(fn_h(P(ah16), P(wh16), None, P(y), *geom, ops.ACT_NONE, 1, 1.0, s)),
+                            "bf16x3": lambda: _lib.check(fn_b(P(ab16), P(wb16), None, P(y), *geom, ops.ACT_NONE, s))}
+            else:
+                variants = {"f16": lambda: _lib.check(fn_h(P(ah16), P(wh16), P(y), *geom, 1, 1.0, s)),
+                            "bf16x3": lambda: _lib.check(fn_b(P(ab16), P(wb16), P(y), *geom, s))}
+        r = ab(variants, args.iters, args.reps, args.warmup)
+        res[tag] = {"launch": "fused" if fusable else "plain convolution (K is split: not fusable)",
+                    "f16_us": r["f16"]["ms"] * 1e3, "f16_us_min_max": [r["f16"]["min"] * 1e3, r["f16"]["max"] * 1e3],
+                    "bf16x3_us": r["bf16x3"]["ms"] * 1e3, "bf16x3_us_min_max": [r["bf16x3"]["min"] * 1e3, r["bf16x3"]["max"] * 1e3],
+                    "speedup": r["bf16x3"]["ms"] / r["f16"]["ms"], "gflop": 50.0 * B * Hs * Hs * Cin * Cout * 1e-9,
+                    "writes": "fp32" if ys is None else "f16: hi plane; bf16x3: both planes"}
+        print(f"  layer {tag}: f16 {res[tag]['f16_us']:.1f} us  bf16x3 {res[tag]['bf16x3_us']:.1f} us  ({res[tag]['speedup']:.2f}x, {res[tag]['launch']})",
+              flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=40, help="calls per timed window")
@@ -238,7 +362,7 @@ def main():
                     help="add the scoring leg at 128x128x3 batch 32: score() with 1 and K draws against the composed path")
     ap.add_argument("--score-only", action="store_true", help="with --score: skip the reconstruct / decode / encode legs")
     ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated subset of: " + ", ".join(SHAPES))
-    ap.add_argument("--precisions", default="bf16x3,f32")
+    ap.add_argument("--precisions", default="bf16x3,f32", help="comma-separated subset of: f16, bf16x3, f32")
     ap.add_argument("--out", default="bench_out/infer.json")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -248,14 +372,25 @@ def main():
            "results": {}, "layers": {}}
     if args.score < 0 or (args.score_only and not args.score):
         raise SystemExit("--score takes a positive K; --score-only needs it")
+    precs = args.precisions.split(",")
+    if any(p not in ("f16", "bf16x3", "f32") for p in precs):
+        raise SystemExit("--precisions takes f16, bf16x3, f32")
+    module_precs = [p for p in precs if p != "f16"]      # (the module path has no one-product mode to compare against)
+    if "f16" in precs:      # first: the alternating-window comparison of the modes, before the long module-path legs
+        doc["modes"], doc["layers_f16"] = {}, {}
+        for name in args.shapes.split(","):
+            C, S, z, B = SHAPES[name]
+            doc["modes"][name] = bench_modes(name, C, S, z, B, precs, args, args.score)
+            if args.layers:
+                doc["layers_f16"][name] = bench_layers_f16(C, S, z, B, args)
     if args.score:
         doc["score"] = {}
         name = "bench_128x128x3_z128_b32"
-        for prec in args.precisions.split(","):
+        for prec in module_precs:
             doc["score"][f"{name}/{prec}"] = bench_score(name, *SHAPES[name], prec, args)
     for name in args.shapes.split(",") if not args.score_only else ():
         C, S, z, B = SHAPES[name]
-        for prec in args.precisions.split(","):
+        for prec in module_precs:
             doc["results"][f"{name}/{prec}"] = bench_shape(name, C, S, z, B, prec, args)
             if args.layers:
                 doc["layers"][f"{name}/{prec}"] = bench_layers(C, S, z, B, prec, args)

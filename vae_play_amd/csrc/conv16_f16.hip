@@ -3,18 +3,23 @@
 #define VP_PCFG_LIBRARY 1
 #include "conv16_impl.h"
 
-// checks `products` and hands it to f as a compile-time constant (std::integral_constant<int, 2 | 3>)
-template <class F>
+// checks `products` and hands it to f as a compile-time constant (std::integral_constant<int, 1 | 2 | 3>).  MIN = 1: the entry points that
+// have the one-product form (gather, scatter); MIN = 2: the statistics epilogue, which exists for the training arithmetics only.
+template <int MIN, class F>
 static int with_products(const char* what, int products, F f) {
-  VP_REQUIRE(products == 2 || products == 3, "%s: products must be 2 or 3", what);
+  VP_REQUIRE(products >= MIN && products <= 3, "%s: products must be %s", what, MIN == 1 ? "1, 2 or 3" : "2 or 3");
+  if constexpr (MIN == 1) if (products == 1) return f(std::integral_constant<int, 1>());
   return products == 2 ? f(std::integral_constant<int, 2>()) : f(std::integral_constant<int, 3>());
 }
-#define VP_PRODUCTS(what, call) with_products(what, products, [&](auto pr) { constexpr int PR = decltype(pr)::value; return call; })
+#define VP_PRODUCTS_FROM(MIN, what, call) with_products<MIN>(what, products, [&](auto pr) { constexpr int PR = decltype(pr)::value; return call; })
+#define VP_PRODUCTS(what, call) VP_PRODUCTS_FROM(1, what, call)
+#define VP_PRODUCTS23(what, call) VP_PRODUCTS_FROM(2, what, call)
 
 extern "C" {
 
 // ---- fp16-pair planes ("f16x2" plans): the same three families with two or three MFMAs per fragment pair (igemm16.h mfma_split) -------
 // Operands are written by the *_fmt producers with format 1; `products` = 3: al*bh + ah*bl + ah*bh (forward layers: ~1e-6 relative),
+// 1: ah*bh (inference: neither lo plane is read; 11 significant bits per operand),
 // 2: (ah + al)*bh (backward layers: the weight operand of the gather / scatter families and the `big` operand of the weight gradient
 // contribute their fp16 hi plane only, ~2e-4 relative per layer).  out_scale multiplies the accumulators (1 / the scale the producer
 // of a gradient operand applied; 1 for activations and weights).
@@ -63,7 +68,7 @@ size_t vp_conv5_stats_f16_workspace_bytes(int family, int B, int Hs, int Ws, int
 int vp_conv5_gather_stats_f16(const void* big_split, const void* w_p0_split, float* small_out, int B, int Hs, int Ws, int Cbig,
                               int Csmall, int stride, int products, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                               float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
-  return VP_PRODUCTS("vp_conv5_gather_stats_f16",
+  return VP_PRODUCTS23("vp_conv5_gather_stats_f16",
                      conv5_stats("vp_conv5_gather_stats_f16", "vp_conv5_stats_f16_workspace_bytes", conv_gather<ProbF16T<true, PR - 1>, FORMS_ALL, TILES_ALL>,
                                  0, arith16<PR>(), true, big_split, w_p0_split, small_out, B, Hs, Ws, Cbig, Csmall, stride,
                                  {eps, momentum, mean, rstd, running_mean, running_var, ws, ws_bytes}, stream));
@@ -72,7 +77,7 @@ int vp_conv5_gather_stats_f16(const void* big_split, const void* w_p0_split, flo
 int vp_conv5_scatter_stats_f16(const void* small_split, const void* w_p1_split, float* big_out, int B, int Hs, int Ws, int Csmall,
                                int Cbig, int stride, int products, float eps, float momentum, float* mean, float* rstd, float* running_mean,
                                float* running_var, void* ws, size_t ws_bytes, vp_stream stream) {
-  return VP_PRODUCTS("vp_conv5_scatter_stats_f16",
+  return VP_PRODUCTS23("vp_conv5_scatter_stats_f16",
                      conv5_stats("vp_conv5_scatter_stats_f16", "vp_conv5_stats_f16_workspace_bytes", conv_scatter<ProbT16T<true, PR - 1>, FORMS_ALL, TILES_ALL>,
                                  1, arith16<PR>(), true, small_split, w_p1_split, big_out, B, Hs, Ws, Cbig, Csmall, stride,
                                  {eps, momentum, mean, rstd, running_mean, running_var, ws, ws_bytes}, stream));

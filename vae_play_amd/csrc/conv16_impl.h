@@ -12,7 +12,7 @@
 using namespace vp;
 
 
-template <int F16> constexpr Arith arith16() { return F16 == 0 ? BF16X3 : (F16 == 2 ? F16_2 : F16_3); }
+template <int F16> constexpr Arith arith16() { return F16 == 0 ? BF16X3 : (F16 == 1 ? F16_1 : (F16 == 2 ? F16_2 : F16_3)); }
 
 // The one-tap-per-workgroup weight gradient on a WgradPlan (WIDE or MAIN): FORMS / TILES name what PW instantiates (igemm16.h)
 template <class PW, unsigned FORMS, unsigned TILES>
@@ -44,7 +44,8 @@ static int wgrad16_rows(const char* what, const WgradPlan& w, const void* big_sp
   return slab_reduce_launch((const float*)ws, dw_ref, g.Cs, g.Cb, slabs, (hipStream_t)stream, g.nt);
 }
 
-// ---- argument checks + dispatch of the three families; F16 = 0: bf16 pairs (three products), 2 | 3: fp16 pairs, products per fragment pair
+// ---- argument checks + dispatch of the three families; F16 = 0: bf16 pairs (three products), 1 | 2 | 3: fp16 planes, products per fragment
+// pair (1: hi planes only, descriptor mode 4 -- gather and scatter; the weight gradient has the two-product form only)
 template <int F16>
 static int gather16(const char* what, const void* big_split, const void* w_p0_split, const float* bias, float* small_out, int B, int Hs,
                     int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride, int act, vp_stream stream, float alpha = 1.f) {
@@ -60,7 +61,8 @@ static int gather16(const char* what, const void* big_split, const void* w_p0_sp
   e.bias = bias; e.act = act; e.alpha = alpha;
 #define VP_G16(PF) conv_gather<PF, FORMS_ALL, TILES_ALL>(what, pl, g, big_split, w_p0_split, small_out, e, stream)
   // fp16-pair planes, f16 = products per fragment pair: always the implicit-GEMM kernels (the halo kernels read bf16 pairs)
-  if constexpr (F16 == 2) return plain5(g) ? VP_G16(ProbF16X) : VP_G16(ProbF16KX);
+  if constexpr (F16 == 1) return plain5(g) ? VP_G16(ProbF16O) : VP_G16(ProbF16KO);
+  else if constexpr (F16 == 2) return plain5(g) ? VP_G16(ProbF16X) : VP_G16(ProbF16KX);
   else if constexpr (F16 == 3) return plain5(g) ? VP_G16(ProbF16H) : VP_G16(ProbF16KH);
   else {
     if (pl.route == ROUTE_HALO)
@@ -83,7 +85,8 @@ static int scatter16(const char* what, const void* small_split, const void* w_p1
   ConvEpi e;
   e.bias = bias; e.alpha = alpha;
 #define VP_S16(PT) conv_scatter<PT, FORMS_ALL, TILES_ALL>(what, pl, g, small_split, w_p1_split, big_out, e, stream)
-  if constexpr (F16 == 2) return plain5(g) ? VP_S16(ProbT16X) : VP_S16(ProbT16KX);
+  if constexpr (F16 == 1) return plain5(g) ? VP_S16(ProbT16O) : VP_S16(ProbT16KO);
+  else if constexpr (F16 == 2) return plain5(g) ? VP_S16(ProbT16X) : VP_S16(ProbT16KX);
   else if constexpr (F16 == 3) return plain5(g) ? VP_S16(ProbT16H) : VP_S16(ProbT16KH);
   else {
     if (pl.route == ROUTE_HALO) return halo_scatter_launch(pl.kind, small_split, w_p1_split, big_out, B, Hs, Ws, Csmall, Cbig, (hipStream_t)stream);

@@ -17,6 +17,7 @@ struct ConvEpi {
   float alpha = 1.f;                // multiplies the accumulators (fp16 planes: undoes a producer's scale)
   float* stat = nullptr;            // BatchNorm statistics slab (igemm16.h epilogue_stats32): K must not be split
   const float* scale = nullptr; const float* shift = nullptr; void* out_split = nullptr;      // is_affine<P> only (igemm16.h AffineEpi)
+  int out_fmt = 0;                  // ... on fp16 planes: the format of out_split (AffineEpi::out_fmt)
 };
 
 // the pipelined kernel's descriptor (igemm16p.h) where ROUTE_PIPELINED exists for P: the plain 5x5 layers on bf16 pairs
@@ -41,6 +42,7 @@ static int conv_exec(const char* what, P& p, const ConvPlan& pl, const ConvGeom&
     p.e.scale = e.scale; p.e.shift = e.shift;
     p.e.out_split = (u16*)e.out_split; p.e.split_plane = n_out;
     p.e.relu = e.act == VP_ACT_RELU ? 1 : 0;
+    p.e.out_fmt = e.out_fmt;
   }
   if (e.stat && pl.nsplit != 1) return fail(VP_ERR_ARG, "%s: this shape splits K", what);
   if (pl.zero_fill && hipMemsetAsync(out, 0, n_out * sizeof(float), s) != hipSuccess) return fail(VP_ERR_LAUNCH, "%s: memset failed", what);

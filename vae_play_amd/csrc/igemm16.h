@@ -71,8 +71,11 @@ struct Lds16 {
 // F family on split planes: A(m=(b,hs,ws), k=(tap,c)) = big[...]; B(n, k) = wp0[n][tap][c]
 template <bool K5, int MODE_ = 0>
 struct ProbF16T {
-  static constexpr int MODE = MODE_;  // 0: bf16 pairs, 3 MFMAs | 1: fp16 pairs, 2 MFMAs | 2: fp16 pairs, 3 MFMAs (see mfma_split) | 3: fp32 (see F32)
-  static constexpr bool X2 = MODE_ == 1, F16 = MODE_ == 1 || MODE_ == 2;
+  static constexpr int MODE = MODE_;  // 0: bf16 pairs, 3 MFMAs | 1: fp16 pairs, 2 MFMAs | 2: fp16 pairs, 3 MFMAs (see mfma_split) | 3: fp32 (see F32) | 4: fp16 hi planes, 1 MFMA (see H1)
+  static constexpr bool X2 = MODE_ == 1, F16 = MODE_ == 1 || MODE_ == 2 || MODE_ == 4;
+  // MODE 4, one product (inference): fp16 planes in format 1 of which ONLY the hi plane of either operand is fetched, staged and read;
+  // a fragment pair is ONE v_mfma_f32_32x32x16_f16(ah, bh).  The LDS image holds one plane per operand.  Gather / scatter families only.
+  static constexpr bool H1 = MODE_ == 4;
   // MODE 3, exact fp32 through this kernel's data path: ONE plane per operand holding fp32 values, addressed in 16-bit units (the
   // host doubles the gathered channel count: [pix][C] fp32 = [pix][2C] u16), a 16-B chunk = 4 floats, a 64-deep K-tile = 32 floats;
   // every fragment pair is contracted by four v_mfma_f32_32x32x2_f32.  Gather / scatter families only.
@@ -180,12 +183,17 @@ using ProbF16X = ProbF16T<true, 1>;
 using ProbF16KX = ProbF16T<false, 1>;
 using ProbF16H = ProbF16T<true, 2>;
 using ProbF16KH = ProbF16T<false, 2>;
+using ProbF16O = ProbF16T<true, 4>;       // one product
+using ProbF16KO = ProbF16T<false, 4>;
 
 // T family on split planes (phase-decomposed transposed conv)
 template <bool K5, int MODE_ = 0>
 struct ProbT16T {
-  static constexpr int MODE = MODE_;  // 0: bf16 pairs, 3 MFMAs | 1: fp16 pairs, 2 MFMAs | 2: fp16 pairs, 3 MFMAs (see mfma_split) | 3: fp32 (see F32)
-  static constexpr bool X2 = MODE_ == 1, F16 = MODE_ == 1 || MODE_ == 2;
+  static constexpr int MODE = MODE_;  // 0: bf16 pairs, 3 MFMAs | 1: fp16 pairs, 2 MFMAs | 2: fp16 pairs, 3 MFMAs (see mfma_split) | 3: fp32 (see F32) | 4: fp16 hi planes, 1 MFMA (see H1)
+  static constexpr bool X2 = MODE_ == 1, F16 = MODE_ == 1 || MODE_ == 2 || MODE_ == 4;
+  // MODE 4, one product (inference): fp16 planes in format 1 of which ONLY the hi plane of either operand is fetched, staged and read;
+  // a fragment pair is ONE v_mfma_f32_32x32x16_f16(ah, bh).  The LDS image holds one plane per operand.  Gather / scatter families only.
+  static constexpr bool H1 = MODE_ == 4;
   // MODE 3, exact fp32 through this kernel's data path: ONE plane per operand holding fp32 values, addressed in 16-bit units (the
   // host doubles the gathered channel count: [pix][C] fp32 = [pix][2C] u16), a 16-B chunk = 4 floats, a 64-deep K-tile = 32 floats;
   // every fragment pair is contracted by four v_mfma_f32_32x32x2_f32.  Gather / scatter families only.
@@ -325,6 +333,8 @@ using ProbT16X = ProbT16T<true, 1>;
 using ProbT16KX = ProbT16T<false, 1>;
 using ProbT16H = ProbT16T<true, 2>;
 using ProbT16KH = ProbT16T<false, 2>;
+using ProbT16O = ProbT16T<true, 4>;
+using ProbT16KO = ProbT16T<false, 4>;
 
 // Affine-activation epilogue (inference: eval-mode BatchNorm + ReLU folded into the convolution).  A gather / scatter descriptor wrapped
 // in ProbAff makes igemm16_kernel end with
@@ -333,10 +343,14 @@ using ProbT16KH = ProbT16T<false, 2>;
 //     split planes of v       if out_split != nullptr (hi at out_split, lo at out_split + split_plane; split.h's rounding)
 // instead of the descriptor's store().  A compile-time property of the descriptor type (is_affine): the instantiations on the plain
 // descriptors do not see it.  K is never split here (a non-linear epilogue cannot be applied to partial sums): nsplit == 1.
+// out_fmt (descriptors on fp16 planes only; the bf16 ones always write bf16 pairs): what out_split receives --
+//   0: bf16 pair, both planes | 1: fp16 pair, both planes (split_f16: saturating at +-65504) | 2: the fp16 hi plane ONLY (the lo plane
+//   of the buffer is not written: the consumer is a one-product layer, which never reads it)
 struct AffineEpi {
   const float* scale; const float* shift;   // [N] fp32
   u16* out_split; size_t split_plane;
   int relu;
+  int out_fmt = 0;
 };
 template <class Base>
 struct ProbAff : Base {
@@ -446,10 +460,13 @@ using ProbW16KX = ProbW16T<false, 1>;
 //   MODE 2 (fp16 pairs): the same three products with v_mfma_f32_32x32x16_f16 (up to 22 significant bits per operand);
 //   MODE 1 (fp16 pairs): a*b ~= al*bh + ah*bh = a*bh, two MFMAs: operand A keeps hi + lo, operand B only its fp16 hi plane
 //                        (11 bits: 2^-12 rms relative rounding per B element); B's lo plane is not read.
+//   MODE 4 (fp16 hi planes): a*b ~= ah*bh, ONE MFMA: 11 significant bits per operand, the product exact in fp32; no lo plane is read.
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 template <int MODE>
 __device__ __forceinline__ f32x16_t mfma_split(const bf16x8_t& ah, const bf16x8_t& al, const bf16x8_t& bh, const bf16x8_t& bl, f32x16_t c) {
-  if constexpr (MODE != 0) {
+  if constexpr (MODE == 4) {
+    c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bh), c, 0, 0, 0);
+  } else if constexpr (MODE != 0) {
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, al), __builtin_bit_cast(f16x8_t, bh), c, 0, 0, 0);
     if constexpr (MODE == 2) c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bl), c, 0, 0, 0);
     c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, ah), __builtin_bit_cast(f16x8_t, bh), c, 0, 0, 0);
@@ -601,6 +618,7 @@ __device__ __forceinline__ void epilogue_stats16(float* __restrict__ stat, int g
 //    [32 rows][32 TN + 8 dwords] (row pitch == 8 dwords mod 16: the two half-waves, four rows apart, write disjoint banks), reads it
 //    back with one lane per (row, 8 channels) -- two 16-B LDS reads -- separates the planes with four v_perm-class operations each
 //    and writes ONE 16-B store per plane: 8 channels of an NHWC row, the 4 or 8 lanes of a row contiguous (64 / 128 B per row).
+// Descriptors on fp16 planes choose the planes' format at run time (AffineEpi::out_fmt); with out_fmt = 2 the lo plane's store is skipped.
 // Call with every wave past its last LDS read of the main loop (the loop ends with a barrier).
 template <class P, int BM, int BN, int WM, int WN, int TM, int TN, int LDS_BYTES>
 __device__ __forceinline__ void epilogue_affine32(const P& p, const typename P::ZCtx& z, f32x16_t (&acc)[TM][TN], unsigned char* lds, int m0,
@@ -648,7 +666,8 @@ __device__ __forceinline__ void epilogue_affine32(const P& p, const typename P::
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             u16_t h, l;
-            split_f32(acc[i][j][r], h, l);
+            if constexpr (P::F16) split_f32(acc[i][j][r], h, l, p.e.out_fmt == 0 ? SPLIT_BF16 : SPLIT_F16);      // (workgroup-uniform)
+            else split_f32(acc[i][j][r], h, l);
             stage[((r & 3) + 8 * (r >> 2) + 4 * lh) * S + 32 * j + li] = (unsigned)h | ((unsigned)l << 16);
           }
         __syncthreads();
@@ -666,7 +685,7 @@ __device__ __forceinline__ void epilogue_affine32(const P& p, const typename P::
           size_t base;
           if (n < p.N && p.out_index(m, 0, z, base)) {      // N % 8 == 0: the 8 channels are inside or outside together
             *reinterpret_cast<u32x4_t*>(p.e.out_split + base + n) = hi;
-            *reinterpret_cast<u32x4_t*>(p.e.out_split + p.e.split_plane + base + n) = lo;
+            if (!P::F16 || p.e.out_fmt != 2) *reinterpret_cast<u32x4_t*>(p.e.out_split + p.e.split_plane + base + n) = lo;
           }
         }
       }
@@ -708,9 +727,15 @@ __global__ void __launch_bounds__(256, (M16 && BM * BN >= 128 * 128) ? 2 : 1) ig
   constexpr int NA = P::A_KM ? NA_KM : NRA * CPT, NB = P::B_KM ? NB_KM : NRB * CPT;
   static_assert(NA >= 1 && NB >= 1, "staging map");
   // (the two-product fp16 mode never stages B's lo plane: its LDS image is one plane -- a third workgroup per CU on the 128x64 tiles)
-  constexpr bool A_LO = !P::F32, B_LO = !P::X2 && !P::F32;      // is the operand's lo plane staged and read?
+  // (the one-product fp16 mode stages neither lo plane: half the LDS image and half the operand fetch per K-tile)
+  constexpr bool ONE = P::MODE == 4;
+  constexpr bool A_LO = !P::F32 && !ONE, B_LO = !P::X2 && !P::F32 && !ONE;      // is the operand's lo plane staged and read?
   static_assert(!P::F32 || (!P::A_KM && !P::B_KM), "fp32 mode: k-contiguous operands only");
-  __shared__ __attribute__((aligned(16))) unsigned char lds[(A_LO ? 2 : 1) * A_PLANE + (B_LO ? 2 : 1) * B_PLANE];
+  static_assert(!ONE || (!P::A_KM && !P::B_KM), "one-product mode: k-contiguous operands only");
+  constexpr int OPERAND_BYTES = (A_LO ? 2 : 1) * A_PLANE + (B_LO ? 2 : 1) * B_PLANE;
+  // one-product tiles are smaller than the affine epilogue's split-store staging region (epilogue_affine32): the array holds the larger
+  constexpr int EPI_BYTES = (ONE && is_affine<P>::value) ? 4 * 32 * (32 * TN + 8) * 4 : 0;
+  __shared__ __attribute__((aligned(16))) unsigned char lds[OPERAND_BYTES > EPI_BYTES ? OPERAND_BYTES : EPI_BYTES];
   unsigned char* As = lds;                   // [plane][...]
   unsigned char* Bs = lds + (A_LO ? 2 : 1) * A_PLANE;
 

@@ -23,7 +23,9 @@ struct PlanSwitches {            // defaults = no variable set (DESIGN.md sectio
   long wgrad5_blocks = WGRAD5_BLOCKS_UNSET;      // VP_WGRAD5_BLOCKS
 };
 
-enum Arith : int { BF16X3 = 0, F16_2, F16_3, F32 };      // bf16 pairs (three products) | fp16 pairs, two | three products | exact fp32
+// bf16 pairs (three products) | fp16 pairs, two | three products | exact fp32 | fp16 hi planes, one product (inference; planned like
+// the other fp16 modes: always ROUTE_STAGED)
+enum Arith : int { BF16X3 = 0, F16_2, F16_3, F32, F16_1 };
 // LEGACY: fp32 shapes that the fast path refuses (igemm.h; conv.hip asks narrow.hip first)
 enum Route : int { ROUTE_LEGACY = 0, ROUTE_HALO, ROUTE_PIPELINED, ROUTE_STAGED };
 enum Epilogue : int { EPI_NONE = 0, EPI_STAT, EPI_AFFINE };      // BatchNorm statistics slab | folded BatchNorm (+ ReLU), inference
@@ -232,9 +234,10 @@ inline ConvPlan plan_stats(int family, Arith ar, int B, int Hs, int Ws, int Cbig
   return plan_conv(family != 0, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), ar, false, ACT_NONE, aligned16, EPI_STAT, sw);
 }
 inline ConvPlan plan_affine(int family, int precision, int B, int Hs, int Ws, int Cbig, int Csmall, int stride, const PlanSwitches& sw) {
-  if ((family != 0 && family != 1) || (precision != 0 && precision != 1)) return ConvPlan();
+  if ((family != 0 && family != 1) || precision < 0 || precision > 2) return ConvPlan();      // 0 bf16x3 | 1 f32 | 2 one-product fp16
   if (B <= 0 || Hs <= 0 || Ws <= 0 || Cbig <= 0 || Csmall <= 0 || (stride != 1 && stride != 2)) return ConvPlan();
-  return plan_conv(family == 1, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), precision ? F32 : BF16X3, false, ACT_NONE, true, EPI_AFFINE, sw);
+  return plan_conv(family == 1, make_geom(B, Hs, Ws, Csmall, Cbig, stride, 5), precision == 1 ? F32 : (precision == 2 ? F16_1 : BF16X3), false, ACT_NONE, true,
+                   EPI_AFFINE, sw);
 }
 
 // ---- weight gradient -----------------------------------------------------------------------------------------------------------

@@ -40,7 +40,10 @@ class FusedVAEInference:
     always ``refresh()``.)  Nothing here writes to the module: parameters, running statistics, ``num_batches_tracked`` and the
     ``training`` flags are never modified, and the result is eval-mode arithmetic whatever ``module.training`` says.
 
-    ``precision``: "bf16x3" (5x5 layers on split-bf16 operands, three MFMAs per product) or "f32" (exact fp32 products).
+    ``precision``: "bf16x3" (5x5 layers on split-bf16 operands, three MFMAs per product), "f32" (exact fp32 products) or "f16"
+    (one product: activations and weights of the 5x5 blocks rounded to fp16 -- 11 significant bits, saturating at +-65504 -- and
+    contracted with ONE fp16 MFMA per fragment pair and fp32 accumulation; the final convolution and the dense layers keep the
+    bf16x3 plan's kernels.  Inference only: the training plans have no such mode.  Measured errors and throughput: DESIGN.md 14.2).
     Inputs of any number of rows run in chunks of ``batch_size``; a short last chunk is padded with zero rows (eval-mode rows are
     independent).  Module I/O is logical NCHW fp32."""
 
@@ -56,8 +59,8 @@ class FusedVAEInference:
         return self
 
     def _init(self, encoder, decoder, batch_size, img_size, channels, precision, plan_only):
-        if precision not in ("bf16x3", "f32"):
-            raise ValueError("precision must be 'bf16x3' or 'f32'")
+        if precision not in ("bf16x3", "f32", "f16"):
+            raise ValueError("precision must be 'bf16x3', 'f32' or 'f16'")
         if batch_size <= 0 or img_size < 16 or img_size & (img_size - 1):
             raise ValueError("batch_size must be positive and img_size a power of two >= 16")
         self.encoder, self.decoder, self.precision = encoder, decoder, precision

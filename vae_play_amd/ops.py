@@ -858,7 +858,8 @@ def unpack_dw_im2col5_f32(dwc, C: int, out: Optional[torch.Tensor] = None):
     return dw
 
 
-# ---- fp16-pair operands: products = 3 (~1e-6 relative) or 2 (two MFMAs per fragment pair, declared tolerance ~2e-4 per layer) ----
+# ---- fp16-pair operands: products = 3 (~1e-6 relative), 2 (two MFMAs per fragment pair, declared tolerance ~2e-4 per layer) or, gather
+# and scatter only, 1 (hi planes only, one MFMA: inference, 11 significant bits per operand) ----
 def conv5_gather_f16(big_split, shape_big, w_p0_split, Cs: int, bias, stride: int, act: int = ACT_NONE, products: int = 2,
                      out_scale: float = 1.0):
     B, Cb, Hb, Wb = shape_big
@@ -897,24 +898,32 @@ def bn_fold(gamma, beta, running_mean, running_var, eps: float):
     return scale, shift, rstd
 
 
+AFFINE_PRECISION = {"bf16x3": 0, "f32": 1, "f16": 2}      # precision codes of vp_conv5_affine_supported
+OUT_BF16_PAIR, OUT_F16_PAIR, OUT_F16_HI = 0, 1, 2         # out_fmt of the vp_conv5_*_affine_f16 entry points
+
+
 def conv5_affine_supported(family: int, precision: str, B: int, Hs: int, Ws: int, Cbig: int, Csmall: int, stride: int) -> bool:
-    """does this launch shape take the affine epilogue?  family 0 = gather, 1 = scatter; precision "bf16x3" | "f32" """
-    return bool(_lib.load().vp_conv5_affine_supported(family, {"bf16x3": 0, "f32": 1}[precision], B, Hs, Ws, Cbig, Csmall, stride))
+    """does this launch shape take the affine epilogue?  family 0 = gather, 1 = scatter; precision "bf16x3" | "f32" | "f16" """
+    return bool(_lib.load().vp_conv5_affine_supported(family, AFFINE_PRECISION[precision], B, Hs, Ws, Cbig, Csmall, stride))
 
 
 def conv5_affine(family: int, precision: str, a, shape_a, w_packed, Cout: int, scale, shift, stride: int, act: int = ACT_RELU,
-                 want_f32: bool = True, want_split: bool = False):
+                 want_f32: bool = True, want_split: bool = False, out_fmt: int = OUT_BF16_PAIR, out_split=None):
     """act(scale * conv(a) + shift) in one launch.  ``a``: the input of logical shape ``shape_a`` (B, Cin, H, W) -- split planes
-    (bf16x3) or a channels_last fp32 tensor (f32); ``w_packed``: P0 (gather) / P1 (scatter) in the same arithmetic.  Returns
-    (fp32 output or None, split planes or None); the f32 entry points refuse ``want_split``."""
+    (bf16x3: bf16 pairs; f16: fp16 planes, of which the one-product contraction reads the hi plane only) or a channels_last fp32
+    tensor (f32); ``w_packed``: P0 (gather) / P1 (scatter) in the same arithmetic.  Returns (fp32 output or None, split planes or
+    None); the f32 entry points refuse ``want_split``.  "f16" only: ``out_fmt`` = what the split planes hold (OUT_BF16_PAIR |
+    OUT_F16_PAIR | OUT_F16_HI: the hi plane only, the lo plane of the buffer is left as it was); ``out_split``: write into this
+    buffer instead of a new one."""
     B, Cin, H, W = shape_a
     Hs, Ws = (H // stride, W // stride) if family == 0 else (H, W)
     Ho, Wo = (Hs, Ws) if family == 0 else (H * stride, W * stride)
     out = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=a.device, memory_format=torch.channels_last) if want_f32 else None
-    out_s = empty_split(B * Cout * Ho * Wo, a) if want_split else None
+    out_s = (out_split if out_split is not None else empty_split(B * Cout * Ho * Wo, a)) if want_split else None
     name = ("vp_conv5_gather_affine_", "vp_conv5_scatter_affine_")[family] + precision
-    pa, pw = (_pv(a), _pv(w_packed)) if precision == "bf16x3" else (_p(a), _p(w_packed))
-    _lib.call(name, pa, pw, _p(scale), _p(shift), _p(out), _pv(out_s), B, Hs, Ws, Cin, Cout, stride, act, _stream())
+    pa, pw = (_pv(a), _pv(w_packed)) if precision != "f32" else (_p(a), _p(w_packed))
+    tail = (out_fmt,) if precision == "f16" else ()
+    _lib.call(name, pa, pw, _p(scale), _p(shift), _p(out), _pv(out_s), B, Hs, Ws, Cin, Cout, stride, act, *tail, _stream())
     return out, out_s
 
 

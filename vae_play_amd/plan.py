@@ -175,6 +175,7 @@ _CONV5 = {
     ("bf16x3", True): ("vp_conv5_gather_stats_bf16x3", "vp_conv5_scatter_stats_bf16x3"),
     ("f16x2", False): ("vp_conv5_gather_f16", "vp_conv5_scatter_f16"),
     ("f16x2", True): ("vp_conv5_gather_stats_f16", "vp_conv5_scatter_stats_f16"),
+    ("f16", False): ("vp_conv5_gather_f16", "vp_conv5_scatter_f16"),       # inference only: no statistics form
 }
 # workspace query of the statistics epilogue by arithmetic (0: the launch shape cannot emit them)
 _CONV5_STATS_WS = {"f32": "vp_conv5_stats_f32_workspace_bytes", "bf16x3": "vp_conv5_stats_workspace_bytes",
@@ -183,11 +184,14 @@ _CONV5_STATS_WS = {"f32": "vp_conv5_stats_f32_workspace_bytes", "bf16x3": "vp_co
 # (the decoder forward on two products measured 3.51 -> 3.375 ms but 40x the ReLU-mask flips, every forward layer on two
 # products puts mu outside the 1e-3 bar: profiles/r02_notes.md section 4)
 FWD_PRODUCTS = 3
+# "f16" (inference) plans: every 16-bit layer contracts the fp16 hi planes with ONE product
+INFER_PRODUCTS = 1
+_F16_ARITHS = ("f16x2", "f16")      # arithmetics of the *_f16 entry points (they take products and out_scale)
 
 
 class PlanBuilder:
-    """What both fused steps build their plans with.  ``precision`` = "f32" | "bf16x3" | "f16x2" (engine.FusedVAEStep documents
-    the modes); ``side_on``: side-stream launches get side slots (else everything stays on the main stream);
+    """What the fused plans are built with.  ``precision`` = "f32" | "bf16x3" | "f16x2" (engine.FusedVAEStep documents the
+    modes) | "f16" (inference only, infer.FusedVAEInference: fp16 planes contracted with one product); ``side_on``: side-stream launches get side slots (else everything stays on the main stream);
     ``wgrad_cus`` = (main, side) CU budget of the 5x5 weight gradients; ``grad_scale16`` and ``sat`` (the sticky saturation
     flag): the fp16 gradient planes of "f16x2" plans.  Buffers are registered in ``step._bufs``."""
 
@@ -195,8 +199,10 @@ class PlanBuilder:
                  fuse_stats: bool = True):
         self.lib = _lib.load()
         self.step, self.dev, self.precision = step, dev, precision
-        self.x3 = precision in ("bf16x3", "f16x2")
+        self.x3 = precision in ("bf16x3", "f16x2", "f16")      # 5x5 layers on split 16-bit operands
         self.x2 = precision == "f16x2"
+        self.h1 = precision == "f16"                            # one-product fp16 (no gradients: forward / eval sections only)
+        self.fp16 = self.x2 or self.h1                          # planes are fp16 (format 1), written by the *_fmt producers
         self.GS = grad_scale16 if self.x2 else 1.0      # scale of gradient planes; 1/GS in the launches that consume them
         self.sat = sat
         self.side_on, self.wgrad_cus, self.fuse_stats = side_on, tuple(wgrad_cus), fuse_stats
@@ -258,7 +264,7 @@ class PlanBuilder:
     def pack(self, weight, p0, p1, Cs, Cb, split, Cs_pad=0, first=False, bf16=False):
         """one job of the batched re-pack; split: planes in the plan's format (bf16=True forces bf16 pairs); ``first``: the
         first encoder block's weight, packed on the main stream when the batch runs on the side stream"""
-        fmt = (2 if (self.x2 and not bf16) else 1) if split else 0
+        fmt = (2 if (self.fp16 and not bf16) else 1) if split else 0
         (self._first_pack_jobs if (first and self.k_pack is not None) else self._pack_jobs).append(
             _lib.PackJob(weight.data_ptr(), p0.data_ptr() if p0 is not None else None, p1.data_ptr() if p1 is not None else None,
                          Cs, Cb, Cs_pad, fmt))
@@ -333,11 +339,11 @@ class PlanBuilder:
 
     def conv5(self, plan, family, arith, a, w, out, geom, products=FWD_PRODUCTS, alpha=1.0, bias=None, act=_ACT_NONE, **kw):
         """5x5 convolution without statistics: family 0 = gather (nn.Conv2d, or a ConvTranspose2d's input gradient; bias and
-        activation in the epilogue), 1 = scatter.  "f16x2" takes the number of fp16 products and the factor the accumulators
-        are multiplied by (1/grad_scale16 for gradient planes)."""
+        activation in the epilogue), 1 = scatter.  "f16x2" and "f16" take the number of fp16 products and the factor the
+        accumulators are multiplied by (1/grad_scale16 for gradient planes)."""
         P = _ptr
         name = _CONV5[(arith, False)][family]
-        tail = (products, alpha) if arith == "f16x2" else ()
+        tail = (products, alpha) if arith in _F16_ARITHS else ()
         if family == 0:
             plan.add(name, P(a), P(w), P(bias), P(out), *geom, act, *tail, **kw)
         else:
@@ -354,22 +360,25 @@ class PlanBuilder:
                  P(rstd), Cn, tag=f"{tag}.fold")
         return scale, shift, rstd
 
-    def conv5_bn_eval(self, plan, tag, family, arith, a, w, geom, bn, folded, y, y_s=None, flops=0.0) -> bool:
+    def conv5_bn_eval(self, plan, tag, family, arith, a, w, geom, bn, folded, y, y_s=None, flops=0.0, out_fmt=ops.OUT_F16_HI) -> bool:
         """5x5 convolution + eval-mode BatchNorm + ReLU writing fp32 ``y`` and / or split planes ``y_s``: ONE launch with the affine
         epilogue where the library takes the launch shape (returns True), else convolution + one normalise pass over a scratch
-        buffer.  ``arith`` = "bf16x3" | "f32"; ``geom`` as conv5's; ``folded`` = bn_fold's result."""
+        buffer.  ``arith`` = "bf16x3" | "f32" | "f16"; ``geom`` as conv5's; ``folded`` = bn_fold's result.  ``out_fmt`` ("f16"
+        only): what the consumer of ``y_s`` reads -- ops.OUT_F16_HI for a one-product layer, ops.OUT_BF16_PAIR for a bf16x3 kernel."""
         P = _ptr
         scale, shift, rstd = folded
         qgeom = geom if family == 0 else (geom[0], geom[1], geom[2], geom[4], geom[3], geom[5])   # query takes (Cbig, Csmall)
-        if self.lib.vp_conv5_affine_supported(family, 1 if arith == "f32" else 0, *qgeom):
+        if self.lib.vp_conv5_affine_supported(family, ops.AFFINE_PRECISION[arith], *qgeom):
             name = ("vp_conv5_gather_affine_", "vp_conv5_scatter_affine_")[family] + arith
-            plan.add(name, P(a), P(w), P(scale), P(shift), P(y), P(y_s), *geom, _ACT_RELU, flops=flops, tag=f"{tag}.fwd")
+            tail = (out_fmt,) if arith == "f16" else ()
+            plan.add(name, P(a), P(w), P(scale), P(shift), P(y), P(y_s), *geom, _ACT_RELU, *tail, flops=flops, tag=f"{tag}.fwd")
             return True
         Bn, Hs, Ws, stride = geom[0], geom[1], geom[2], geom[5]
         Cout = geom[4]
         R = Bn * Hs * Ws * (stride * stride if family == 1 else 1)
         c = self.buf(f"{tag}.c", R * Cout)
-        self.conv5(plan, family, arith, a, w, c, geom, flops=flops, tag=f"{tag}.fwd")
+        self.conv5(plan, family, arith, a, w, c, geom, products=INFER_PRODUCTS if arith == "f16" else FWD_PRODUCTS, flops=flops,
+                   tag=f"{tag}.fwd")
         self.bn_eval(plan, tag, c, R, Cout, bn, rstd, y, y_s)
         return False
 
@@ -379,6 +388,9 @@ class PlanBuilder:
         if y_s is None:
             plan.add("vp_bn_act_fwd_f32", P(x), P(bn.running_mean), P(rstd), P(bn.weight), P(bn.bias), P(y), R, Cn, _ACT_RELU, 0.0,
                      tag=f"{tag}.bn")
+        elif self.fp16:
+            plan.add("vp_bn_act_fwd_split_fmt_f32", P(x), P(bn.running_mean), P(rstd), P(bn.weight), P(bn.bias), P(y), P(y_s), R, Cn,
+                     _ACT_RELU, 0.0, ops.SPLIT_F16, tag=f"{tag}.bn")
         else:
             plan.add("vp_bn_act_fwd_split_f32", P(x), P(bn.running_mean), P(rstd), P(bn.weight), P(bn.bias), P(y), P(y_s), R, Cn,
                      _ACT_RELU, 0.0, tag=f"{tag}.bn")

@@ -15,7 +15,7 @@ from __future__ import annotations
 from types import SimpleNamespace
 
 from . import ops
-from .plan import FWD_PRODUCTS, PlanBuilder, _Plan, _ptr as P, grad_of
+from .plan import FWD_PRODUCTS, INFER_PRODUCTS, PlanBuilder, _Plan, _ptr as P, grad_of
 
 _ACT_NONE, _ACT_SIGMOID = ops.ACT_NONE, ops.ACT_SIGMOID
 
@@ -37,6 +37,8 @@ _STEM = {
                "vp_conv_wgrad_bf16x3_workspace_bytes"),
     "f16x2": ("vp_im2col5s2_split_fmt_f32", "vp_pack_w_im2col5_split_fmt", "vp_conv_gather_f16", "vp_conv_wgrad_f16x2",
               "vp_conv_wgrad_bf16x3_workspace_bytes"),
+    # one-product fp16 (inference): the fp16 producers and the generic-geometry gather with products = 1; it takes no gradient
+    "f16": ("vp_im2col5s2_split_fmt_f32", "vp_pack_w_im2col5_split_fmt", "vp_conv_gather_f16", None, None),
     # exact f32: the same im2col as plain fp32, both 1x1 layers on the fp32-MFMA kernels (the 3-channel implicit GEMM and the VALU
     # weight gradient took 48 + 67 us at the benchmark shard, the two 1x1 layers 36 + 40 + 20 us of im2col / re-order: 7.63 -> 7.60 ms)
     "f32": ("vp_im2col5s2_f32", "vp_pack_w_im2col5_f32", "vp_conv_gather_f32", "vp_conv_wgrad_f32", "vp_conv_wgrad_workspace_bytes"),
@@ -68,11 +70,11 @@ class Im2colStem:
     def _conv(self, plan: _Plan, pack_plan: _Plan):
         b, Bn, Hs, S = self.b, self.Bn, self.Hs, self.S
         im2col, pack, gather = _STEM[b.precision][:3]
-        fmt = (1,) if b.x2 else ()          # VP_SPLIT_F16
+        fmt = (ops.SPLIT_F16,) if b.fp16 else ()
         plan.add(im2col, P(self.image), P(self.xcol), Bn, self.Cin, S, S, 1, *fmt)
         pack_plan.add(pack, P(self.blk.conv.weight), P(self.w0), self.Cout, self.Cin, *fmt)
         plan.add(gather, P(self.xcol), P(self.w0), None, P(self.c), Bn, Hs, Hs, Hs, Hs, self.KC, self.Cout, 1, 1, _ACT_NONE,
-                 *((FWD_PRODUCTS, 1.0) if b.x2 else ()), flops=self.fl, tag=f"{self.tag}.fwd")
+                 *(((INFER_PRODUCTS if b.h1 else FWD_PRODUCTS), 1.0) if b.fp16 else ()), flops=self.fl, tag=f"{self.tag}.fwd")
 
     def fwd(self, plan: _Plan):
         self._conv(plan, plan)
@@ -137,8 +139,9 @@ class GatherBlock:
 
     def fwd_eval(self, plan: _Plan, prep: _Plan):
         folded = self.b.bn_fold(prep, self.tag, self.bn)
+        # ("f16": every consumer of a gather block's planes is a one-product layer -- the fp16 hi plane only)
         self.fused = self.b.conv5_bn_eval(plan, self.tag, 0, self.arith, self.src, self.p0, self.geom, self.bn, folded, self.a, self.a_s,
-                                          flops=self.fl)
+                                          flops=self.fl, out_fmt=ops.OUT_F16_HI)
 
     def bwd(self, plan: _Plan, cur, other, pre_split=None):
         """dy in ``cur`` (fp32 NHWC) -> dx in ``cur`` (``other``: scratch of the fp32 form).  ``pre_split(plane)`` stands in for the
@@ -198,10 +201,12 @@ def scatter_packs(b: PlanBuilder, tag: str, blk, train: bool = True):
 
 
 class ScatterBlock:
-    """ConvTranspose2d 5x5 stride 2 + BatchNorm + ReLU, one pass; ``Hs`` = input side, ``packs`` = scatter_packs(...)."""
+    """ConvTranspose2d 5x5 stride 2 + BatchNorm + ReLU, one pass; ``Hs`` = input side, ``packs`` = scatter_packs(...).  ``out_fmt``
+    ("f16" eval plans): the format its consumer reads -- a one-product layer the fp16 hi plane, the final convolution (a bf16x3 / fp32
+    kernel) bf16 pairs."""
 
-    def __init__(self, b: PlanBuilder, tag: str, blk, Bn: int, Hs: int, src, src_s, out16: bool, packs):
-        self.b, self.tag, self.blk, self.bn = b, tag, blk, blk.bn
+    def __init__(self, b: PlanBuilder, tag: str, blk, Bn: int, Hs: int, src, src_s, out16: bool, packs, out_fmt: int = ops.OUT_F16_HI):
+        self.b, self.tag, self.blk, self.bn, self.out_fmt = b, tag, blk, blk.bn, out_fmt
         self.Cin, self.Cout = blk.conv.weight.shape[:2]
         self.Bn, self.Hs, self.R = Bn, Hs, Bn * 4 * Hs * Hs
         self.p0, self.p1, self.is16 = packs
@@ -218,7 +223,7 @@ class ScatterBlock:
     def fwd_eval(self, plan: _Plan, prep: _Plan):
         folded = self.b.bn_fold(prep, self.tag, self.bn)
         self.fused = self.b.conv5_bn_eval(plan, self.tag, 1, self.arith, self.src, self.p1, self.geom, self.bn, folded, self.u, self.u_s,
-                                          flops=self.fl)
+                                          flops=self.fl, out_fmt=self.out_fmt)
 
     def bwd(self, plan: _Plan, cur, other, gfn=grad_of):
         """dy in ``cur`` -> dx in ``cur``; ``gfn``: where a parameter's gradient lives (the shadow arena of a second pass)"""
@@ -384,15 +389,16 @@ class DecoderTrunk:
         else:
             b.bn_eval(plan, f"{tag}.fc", ps.d, Bn, F1, self.fc_bn, b.bn_fold(prep, f"{tag}.fc", self.fc_bn)[2], ps.db)
         src, src_s = _outputs(b, f"{tag}.in", Bn * F1, self.packs[0][2])
-        if b.x2:
-            plan.add("vp_nchw_to_nhwc_split_fmt_f32", P(ps.db), P(src), P(src_s), Bn, self.size, 8, 8, 1)      # VP_SPLIT_F16
+        if b.fp16:
+            plan.add("vp_nchw_to_nhwc_split_fmt_f32", P(ps.db), P(src), P(src_s), Bn, self.size, 8, 8, ops.SPLIT_F16)
         else:
             plan.add("vp_nchw_to_nhwc_split_f32", P(ps.db), P(src), P(src_s), Bn, self.size, 8, 8)
         ps.blocks = []
         for i in range(self.L):
             # the last block feeds the final conv in fp32 (its image side runs on the narrow / edge kernels)
             out16 = i + 1 < self.L and self.packs[i + 1][2]
-            blk = ScatterBlock(b, f"{tag}{i}", self.dec.conv[i], Bn, 8 << i, src, src_s, out16, self.packs[i])
+            out_fmt = ops.OUT_F16_HI if i + 1 < self.L else ops.OUT_BF16_PAIR      # the final convolution keeps its bf16x3 / fp32 kernel
+            blk = ScatterBlock(b, f"{tag}{i}", self.dec.conv[i], Bn, 8 << i, src, src_s, out16, self.packs[i], out_fmt)
             if self.train:
                 blk.fwd(plan)
             else:

@@ -346,6 +346,30 @@ int vp_latent_iw_fwd_f32(const float* mu, const float* logvar, const float* eps,
  * iwae[b] = max_k logw + log(sum_k exp(logw - max)) - log K; K = 1 returns logw[b][0] exactly */
 int vp_iw_bound_f32(const float* nbce, const float* lr, int B, int K, float* logw, float* iwae, vp_stream stream);
 
+/* ---- latent projection through a frozen eval-mode decoder (vae_play_amd.infer.FusedVAEInference.project / decode_grad) ------ */
+/* New functionality, no counterpart in the reference.  Bit-reproducible: fixed-order sums, no atomics (csrc/project.hip). */
+/* Backward through u = relu(scale*c + shift) (a block with its eval-mode BatchNorm folded) evaluated from the OUTPUT u:
+ * dx[r][ch] = (dy[r][ch] * scale[ch]) * (u[r][ch] > 0 ? 1 : 0) over an [R][C] (NHWC) view.  u is given as fp32 (u) or as bf16 split
+ * planes (u_split; the mask is hi + lo > 0), exactly one of the two.  dx (fp32) and / or dx_split (the planes vp_split_f32 makes of
+ * that fp32 result) are written; dx may alias dy.  16-byte accesses when C % 4 == 0 and the pointers are aligned, else scalar. */
+int vp_affine_relu_bwd_f32(const float* dy, const float* u, const void* u_split, const float* scale, float* dx, void* dx_split,
+                           size_t R, int C, vp_stream stream);
+/* out[r] = sum_i mask * -[t*max(log p,-100) + (1-t)*max(log(1-p),-100)] and dlogit = mask * (p - t) (the convention of
+ * vp_bce_sigmoid_bwd_f32) in one read of p, t, mask: dense [rows][n] in one memory order.  mask == NULL: all ones, and out carries
+ * the bits vp_bce_rows_f32 returns on the same p and t.  ws >= vp_bce_masked_rows_bwd_workspace_bytes(rows, n). */
+size_t vp_bce_masked_rows_bwd_workspace_bytes(int rows, int n);
+int vp_bce_masked_rows_bwd_f32(const float* p, const float* t, const float* mask, int rows, int n, float* out, float* dlogit, void* ws,
+                               size_t ws_bytes, vp_stream stream);
+/* One torch.optim.Adam step (no amsgrad, no weight decay) on z [rows][Z] with moments m, v and gradient g + prior_weight*z.  The
+ * step count is READ FROM DEVICE MEMORY: step_count[0] = steps taken so far, this call is step step_count[0] + 1, so that one
+ * captured graph serves any number of iterations.  The counter is advanced by a separate one-thread launch that this call enqueues
+ * AFTER the update, never by the update itself.  prior (may be NULL): prior[r] = prior_weight/2 * |z_r|^2 of the z that was read.
+ * With prior_weight = 0 the update writes the bits vp_adam_f32 writes at the same step with grad_scale = 1 on the same rows * Z
+ * elements (below that kernel's streaming-loop threshold of 16.7 M elements).
+ * g, m, v and step_count all NULL: no update, prior alone. */
+int vp_latent_adam_f32(float* z, const float* g, float* m, float* v, int* step_count, int rows, int Z, float lr, float beta1,
+                       float beta2, float eps, float prior_weight, float* prior, vp_stream stream);
+
 /* ---- per-pixel BCE ------------------------------------------------------------------------ */
 /* out[0] = sum_i -[t*max(log p,-100) + (1-t)*max(log(1-p),-100)]  (torch F.binary_cross_entropy,
  * reduction='sum'; call form train_BE_font.py:107).  p and t may have different memory order only

@@ -23,7 +23,15 @@ every named precision over ONE model, eager and replayed, alternating in the sam
 spread max - min over the windows, and whether f16 beats bf16x3 by more than the sum of both spreads.  ``--layers`` then also lists
 every 5x5 stride-2 layer's launch in f16 next to bf16x3 (key ``layers_f16``).  The module-path legs run for bf16x3 and f32 as before.
 
+``--project STEPS`` adds, per shape and precision (bf16x3, f32), latent projection: ``FusedVAEInference.project`` with STEPS
+iterations (eager, and replayed as a hipGraph) against the drop-in modules in ``.eval()`` under torch autograd with
+``torch.optim.Adam`` on z (the decoder's parameters frozen, so autograd takes the input gradient alone), in the same alternating
+windows: projections/s, microseconds per iteration, and whether the fused iteration is faster by more than the spread of the windows
+(key ``project``).  Per launch of one iteration it also lists the time between device events around it (``launches``: where the
+iteration's time goes).
+
     python tools/bench_infer.py --out bench_out/infer.json
+    python tools/bench_infer.py --project 20 --project-only --iters 5 --out bench_out/infer_project.json
     python tools/bench_infer.py --precisions f16,bf16x3,f32 --layers --score 8 --out bench_out/infer_f16.json
     python tools/bench_infer.py --score 8 --score-only --out bench_out/infer_score.json
 """
@@ -171,6 +179,93 @@ def bench_score(name, C, S, z, B, prec, args):
                       f"graph {r['fused_graph']['ms']:.3f} [{r['fused_graph']['min']:.3f}, {r['fused_graph']['max']:.3f}]", flush=True)
     finally:
         V.set_conv_precision("f32")
+    return out
+
+
+def project_launches(inf, reps=5):
+    """per launch of the "project" list: median microseconds between device events around it, in launch order"""
+    names = {c[0] for p in inf._plans["project"] for c in p.calls}
+    runs = []
+    for _ in range(reps):
+        timers = {"names": names, "events": []}
+        s = torch.cuda.current_stream().cuda_stream
+        for p in inf._plans["project"]:
+            p.run(s, timers=timers)
+        torch.cuda.synchronize()
+        runs.append([(n, tag, e0.elapsed_time(e1) * 1e3) for n, tag, _, e0, e1 in timers["events"]])
+    return [{"launch": n, "tag": tag, "us": statistics.median(r[i][2] for r in runs)} for i, (n, tag, _) in enumerate(runs[0])]
+
+
+def bench_project(name, C, S, z, B, prec, args):
+    """``--project STEPS``: FusedVAEInference.project (eager, replayed) against the modules in eval mode under torch autograd with
+    torch.optim.Adam on z, all from the same z0 towards the same target, in alternating windows"""
+    import torch.nn.functional as F
+    import vae_play_amd as V
+    steps, lr, pw = args.project, 0.05, 1.0
+    torch.manual_seed(0)
+    vae = V.VAE(S, z, C).cuda().eval()
+    randomise_bn(vae, 1)
+    g = torch.Generator().manual_seed(2)
+    z0 = torch.randn((B, z), generator=g).cuda()
+    eager = V.FusedVAEInference(vae, B, S, C, precision=prec)
+    x = eager.decode(torch.randn((B, z), generator=g).cuda())         # a target the model can reach
+    graph = V.FusedVAEInference(vae, B, S, C, precision=prec)
+    graph.enable_projection()
+    graph.capture()
+    frozen = [p for p in vae.decoder.parameters() if p.requires_grad]
+    for p in frozen:
+        p.requires_grad_(False)
+    V.set_conv_precision(prec)
+
+    def modules():
+        zt = z0.clone().requires_grad_(True)
+        opt = torch.optim.Adam([zt], lr=lr)
+        for _ in range(steps):
+            opt.zero_grad(set_to_none=True)
+            loss = F.binary_cross_entropy(vae.decoder(zt), x, reduction="sum") + 0.5 * pw * (zt * zt).sum()
+            loss.backward()
+            opt.step()
+        with torch.no_grad():
+            xt = vae.decoder(zt)
+            return zt.detach(), xt, F.binary_cross_entropy(xt, x, reduction="none").flatten(1).sum(1) + 0.5 * pw * (zt * zt).sum(1)
+
+    try:
+        kw = dict(steps=steps, lr=lr, z0=z0, prior_weight=pw)
+        ref, got = modules(), eager.project(x, **kw)
+        r = _with_spread(ab({"modules_autograd": modules, "fused": lambda: eager.project(x, **kw),
+                             "fused_graph": lambda: graph.project(x, **kw)}, args.iters, args.reps, args.warmup), B, "projections_per_s")
+        for v in r.values():
+            v["us_per_iteration"] = v["ms"] * 1e3 / steps
+        out = dict(r)
+        out["steps"] = steps
+        # the paths compute the same thing (recorded, not asserted: the parity tests assert)
+        out["max_rel_diff_fused_vs_modules_loss"] = ((got["loss"] - ref[2]).abs() / ref[2].abs()).max().item()
+        out["max_abs_diff_fused_vs_modules_z"] = (got["z"] - ref[0]).abs().max().item()
+        # graph against eager AFTER the timing loops, as the scoring leg does (DESIGN.md section 14.1), and a graph captured only now
+        after_e, after_g = eager.project(x, **kw), graph.project(x, **kw)
+        fresh = V.FusedVAEInference(vae, B, S, C, precision=prec)
+        fresh.enable_projection()
+        fresh.capture()
+        after_f = fresh.project(x, **kw)
+        out["graph_equals_eager"] = all(bool(torch.equal(after_g[k], after_e[k])) for k in after_e)
+        out["fresh_graph_equals_eager"] = all(bool(torch.equal(after_f[k], after_e[k])) for k in after_e)
+        out["eager_equals_its_first_call"] = all(bool(torch.equal(after_e[k], got[k])) for k in got)
+        out["max_abs_diff_graph_vs_eager"] = {k: (after_g[k] - after_e[k]).abs().max().item() for k in after_e}
+        for k in ("fused", "fused_graph"):
+            saved, spread = r["modules_autograd"]["ms"] - r[k]["ms"], r["modules_autograd"]["spread_ms"] + r[k]["spread_ms"]
+            out[k + "_vs_modules"] = {"speedup": r["modules_autograd"]["ms"] / r[k]["ms"], "saved_ms": saved, "sum_of_spreads_ms": spread,
+                                      "faster_by_more_than_spreads": bool(saved > spread)}
+        out["launches"] = project_launches(eager)
+        for k in ("modules_autograd", "fused", "fused_graph"):
+            v = r[k]
+            print(f"{name} {prec} project x{steps} {k}: {v['ms']:.2f} ms [{v['min']:.2f}, {v['max']:.2f}]  {v['us_per_iteration']:.0f} us/iteration  "
+                  f"{v['projections_per_s']:.0f} projections/s", flush=True)
+        top = max(out["launches"], key=lambda c: c["us"])
+        print(f"{name} {prec} project: fused vs modules {out['fused_vs_modules']}; largest launch {top}", flush=True)
+    finally:
+        V.set_conv_precision("f32")
+        for p in frozen:
+            p.requires_grad_(True)
     return out
 
 
@@ -361,6 +456,9 @@ def main():
     ap.add_argument("--score", type=int, default=0, metavar="K",
                     help="add the scoring leg at 128x128x3 batch 32: score() with 1 and K draws against the composed path")
     ap.add_argument("--score-only", action="store_true", help="with --score: skip the reconstruct / decode / encode legs")
+    ap.add_argument("--project", type=int, default=0, metavar="STEPS",
+                    help="add the projection leg: project() with STEPS iterations against the modules under autograd + torch.optim.Adam")
+    ap.add_argument("--project-only", action="store_true", help="with --project: skip every other leg")
     ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated subset of: " + ", ".join(SHAPES))
     ap.add_argument("--precisions", default="bf16x3,f32", help="comma-separated subset of: f16, bf16x3, f32")
     ap.add_argument("--out", default="bench_out/infer.json")
@@ -376,19 +474,26 @@ def main():
     if any(p not in ("f16", "bf16x3", "f32") for p in precs):
         raise SystemExit("--precisions takes f16, bf16x3, f32")
     module_precs = [p for p in precs if p != "f16"]      # (the module path has no one-product mode to compare against)
-    if "f16" in precs:      # first: the alternating-window comparison of the modes, before the long module-path legs
+    if args.project < 0 or (args.project_only and not args.project):
+        raise SystemExit("--project takes a positive STEPS; --project-only needs it")
+    if args.project:
+        doc["project"] = {}
+        for name in args.shapes.split(","):
+            for prec in module_precs:       # ("f16" plans refuse projection)
+                doc["project"][f"{name}/{prec}"] = bench_project(name, *SHAPES[name], prec, args)
+    if "f16" in precs and not args.project_only:      # first: the alternating-window comparison of the modes, before the long module-path legs
         doc["modes"], doc["layers_f16"] = {}, {}
         for name in args.shapes.split(","):
             C, S, z, B = SHAPES[name]
             doc["modes"][name] = bench_modes(name, C, S, z, B, precs, args, args.score)
             if args.layers:
                 doc["layers_f16"][name] = bench_layers_f16(C, S, z, B, args)
-    if args.score:
+    if args.score and not args.project_only:
         doc["score"] = {}
         name = "bench_128x128x3_z128_b32"
         for prec in module_precs:
             doc["score"][f"{name}/{prec}"] = bench_score(name, *SHAPES[name], prec, args)
-    for name in args.shapes.split(",") if not args.score_only else ():
+    for name in args.shapes.split(",") if not (args.score_only or args.project_only) else ():
         C, S, z, B = SHAPES[name]
         for prec in module_precs:
             doc["results"][f"{name}/{prec}"] = bench_shape(name, C, S, z, B, prec, args)

@@ -132,6 +132,10 @@ SIGNATURES = {
     "vp_bce_rows_f32": (c_int, [P, P, c_int, c_int, P, P, c_size_t, P]),
     "vp_latent_iw_fwd_f32": (c_int, [P, P, P, P, P, P, c_int, c_int, P]),
     "vp_iw_bound_f32": (c_int, [P, P, c_int, c_int, P, P, P]),
+    "vp_affine_relu_bwd_f32": (c_int, [P, P, P, P, P, P, c_size_t, c_int, P]),
+    "vp_bce_masked_rows_bwd_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "vp_bce_masked_rows_bwd_f32": (c_int, [P, P, P, c_int, c_int, P, P, P, c_size_t, P]),
+    "vp_latent_adam_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P, P]),
     "vp_reduce_workspace_bytes": (c_size_t, [c_size_t]),
     "vp_bce_sum_f32": (c_int, [P, P, c_size_t, P, P, c_size_t, P]),
     "vp_bce_bwd_f32": (c_int, [P, P, P, c_float, P, c_size_t, P]),

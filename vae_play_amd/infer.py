@@ -17,6 +17,12 @@ composition of Encoder (models/networks.py:72-78), reparameterize (:228-231) and
 per-pixel ``F.binary_cross_entropy``, summed over the image), the KL term (models/networks.py:270), their sum (the ELBO) and the
 K-sample importance-weighted bound.  The reference has no evaluation loop with a loss; the importance-weighted bound is new
 functionality, not a port.  It reuses the launches above -- encode once, decode K times -- plus the three kernels of csrc/score.hip.
+
+``project`` / ``decode_grad`` search the latent space for a given image: the gradient of the (optionally pixel-masked) reconstruction
+term with respect to z through the frozen eval-mode decoder, and Adam on z with a Gaussian prior -- inversion, and with a mask
+inpainting and occlusion-robust anomaly scoring.  Like the importance-weighted bound it has no counterpart in the reference: new
+functionality, not a port.  One iteration is the decode list, three kernels of csrc/project.hip and the training plans' input-gradient
+convolutions, as one replayable launch list.
 """
 from __future__ import annotations
 
@@ -74,6 +80,7 @@ class FusedVAEInference:
         self._bufs: Dict[str, torch.Tensor] = {}
         self._graphs: Dict[str, "torch.cuda.CUDAGraph"] = {}
         self._score: Optional[SimpleNamespace] = None       # the scoring buffers: none until enable_scoring() / the first score()
+        self._proj: Optional[SimpleNamespace] = None        # the projection buffers and lists: none until enable_projection()
         self._build()
         if not plan_only:
             self.refresh()
@@ -119,16 +126,20 @@ class FusedVAEInference:
             self.x_tilde = xt_nhwc.view(B, C, S, S)
         b.finish(prep)      # the batched weight re-pack at the head of ``prep``; the dense layers' workspace
         self._prep = prep
+        self._trunk, self._dec_pass, self._xt_nhwc = trunk, dec_pass, xt_nhwc       # what enable_projection() differentiates
         self._plans = {"encode": (p_enc,), "decode": (p_dec,), "reconstruct": (p_enc, p_lat, p_dec)}
 
     # ---- execution ---------------------------------------------------------------------------
     def refresh(self) -> None:
         """Re-read the model: pack the convolution weights and fold every BatchNorm's running statistics and affine parameters into
-        the plan's constants.  Runs when the plan is built; call it again after the module's parameters or buffers changed.
+        the plan's constants (and, once projection is enabled, its input-gradient packs; Adam's state is left alone).  Runs when the
+        plan is built; call it again after the module's parameters or buffers changed.
         Graphs captured before are captured again: they replay the same buffers and would see the new constants, but replays of a
         graph instantiated BEFORE the eager re-pack launches were observed to go wrong on MI355X / ROCm (the split-K layer's
         memset + atomic-add pair produced garbage, deterministically, while the eager list stayed right)."""
         self._prep.run(torch.cuda.current_stream().cuda_stream)
+        if self._proj is not None:
+            self._proj.prep.run(torch.cuda.current_stream().cuda_stream)      # the projection's own packs; nothing else of it is reset
         if self._graphs:
             self._graphs = {}
             self.capture()
@@ -143,9 +154,9 @@ class FusedVAEInference:
             plan.run(s)
 
     def capture(self, warmup: int = 2):
-        """Capture encode, decode and reconstruct -- and the scoring lists built so far (``score``) -- into one hipGraph each
-        (linear launch lists, no allocation) and replay them from then on; the results are bit-identical to the eager launches.
-        A scoring list first used after this is captured when it is built."""
+        """Capture encode, decode and reconstruct -- and the scoring and projection lists built so far (``score``, ``project``) --
+        into one hipGraph each (linear launch lists, no allocation) and replay them from then on; the results are bit-identical to
+        the eager launches.  A scoring or projection list first used after this is captured when it is built."""
         self._graphs = self._capture(list(self._plans), warmup)
         return self._graphs
 
@@ -328,6 +339,197 @@ class FusedVAEInference:
             kl[i0:i0 + m].copy_(s.kl[:m])
             iwae[i0:i0 + m].copy_(s.iwae[:m])
         return {"bce": bce, "kl": kl, "logw": logw, "elbo": -(bce.mean(1) + kl), "iwae": iwae}
+
+    # ---- latent projection: the decoder's input gradient and Adam on z ----------------------------------------------------------
+    _PROJECT_DEFAULTS = (0.05, 0.9, 0.999, 1e-8, 1.0)        # lr, beta1, beta2, eps, prior_weight of ``project``
+
+    def enable_projection(self) -> None:
+        """Allocate and plan what ``project`` / ``decode_grad`` need (they call this themselves on first use).  A plan that never
+        projects owns none of it: ``_bufs`` and the encode / decode / reconstruct / score lists of such a plan are what they were
+        before projection existed.  Everything new is registered like every other buffer (``PlanBuilder.buf / sbuf / ws``) under a
+        ``project.`` prefix: the gather-family packs of the decoder blocks (the eval plan owns the scatter family only), the gradient
+        ping-pong buffers and the split gradient plane, Adam's moments and its step counter, and NHWC copies of target and mask when
+        the image has more than one channel.
+
+        "f16" plans refuse: their activations are fp16 hi planes alone, which flush small positive values to zero, so the ReLU mask
+        is not recoverable from a block's output, and there are no one-product input-gradient kernels."""
+        if self._proj is not None:
+            return
+        if self.precision == "f16":
+            raise NotImplementedError("FusedVAEInference: projection needs a 'bf16x3' or 'f32' plan (an 'f16' plan keeps fp16 hi planes "
+                                      "only: the ReLU masks are not recoverable from them, and no one-product gradient kernels exist)")
+        B, S, C, Z, P = self.B, self.S, self.C, self.Z, _ptr
+        trunk, ps = self._trunk, self._dec_pass
+        n = C * S * S
+        b = PlanBuilder(self, self.dev, self.precision, side_on=False, wgrad_cus=(0, 0))
+        q = SimpleNamespace(n=n, hyper=None)
+        # the input-gradient packs
+        p0s = []
+        for i, blk in enumerate(ps.blocks):
+            alloc, sfx = (b.sbuf, "s") if blk.is16 else (b.buf, "")
+            p0s.append(alloc(f"project.dec{i}.p0{sfx}", blk.Cin * 25 * blk.Cout))
+            b.pack(blk.blk.conv.weight, p0s[-1], None, blk.Cin, blk.Cout, blk.is16)
+        fin, fin_p1 = trunk.fin, None
+        if not fin.edge:
+            fin_p1 = b.buf("project.fin.p1", fin.Cf * 25 * C)
+            b.pack(fin.conv.weight, None, fin_p1, C, fin.Cf, False)
+        # target, mask, objective
+        q.mask = b.buf("project.mask", B, C, S, S)
+        load = _Plan()
+        if C > 1:
+            q.x_nhwc, q.mask_nhwc = b.buf("project.x_nhwc", B * n), b.buf("project.mask_nhwc", B * n)
+            load.add("vp_nchw_to_nhwc_f32", P(self.x_nchw), P(q.x_nhwc), B, C, S, S)
+            load.add("vp_nchw_to_nhwc_f32", P(q.mask), P(q.mask_nhwc), B, C, S, S)
+        else:
+            q.x_nhwc, q.mask_nhwc = self.x_nchw, q.mask
+        q.bce, q.prior = b.buf("project.bce", B), b.buf("project.prior", B)
+        dlogit = b.buf("project.dlogit", B * n)
+        ws = b.ws("project.bce.ws", b.lib.vp_bce_masked_rows_bwd_workspace_bytes(B, n))
+        bce = _Plan()
+        bce.add("vp_bce_masked_rows_bwd_f32", P(self._xt_nhwc), P(q.x_nhwc), P(q.mask_nhwc), B, n, P(q.bce), P(dlogit), P(ws),
+                ws.numel() * 4)
+        # the walk back to z
+        n_g = max([B * trunk.F1] + [blk.R * blk.Cout for blk in ps.blocks])
+        cur, other = b.buf("project.gA", n_g), b.buf("project.gB", n_g)
+        n_s = max([0] + [blk.R * blk.Cout for blk in ps.blocks if blk.is16])
+        g_s = b.sbuf("project.gS", n_s) if n_s else None
+        q.dz = b.buf("project.dz", B, Z)
+        walk = _Plan()
+        trunk.bwd_eval(walk, b, ps, dlogit, cur, other, g_s, p0s, q.dz, fin_p1)
+        # Adam's state; the step counter is an int32 in device memory
+        q.m, q.v = b.buf("project.m", B, Z), b.buf("project.v", B, Z)
+        q.step = b.buf("project.step", 1).view(torch.int32)
+        q.prep = _Plan()
+        b.finish(q.prep, prefix="project.")
+        q.p_bce, q.walk = bce, walk
+        self._proj = q
+        if load.calls:
+            self._plans["project.load"] = (load,)
+        self._project_lists(*self._PROJECT_DEFAULTS)
+        if self.dev.type == "cuda":
+            q.prep.run(torch.cuda.current_stream().cuda_stream)
+
+    def _project_lists(self, lr: float, beta1: float, beta2: float, eps: float, prior_weight: float) -> None:
+        """The launch lists that end in a launch with these hyper-parameters in its arguments, rebuilt (and captured again) when they
+        change:
+          "project"       one iteration: the decode list, the masked per-image BCE with dlogit, the input-gradient walk to dz, the latent
+                          update (which also leaves the prior term of the z it read)
+          "project.grad"  the same without the update (``decode_grad``)
+          "project.loss"  the decode list, the BCE and the prior term: the loss at a z"""
+        q, P = self._proj, _ptr
+        hyper = (float(lr), float(beta1), float(beta2), float(eps), float(prior_weight))
+        if q.hyper == hyper:
+            return
+        (p_dec,) = self._plans["decode"]
+        adam, prior = _Plan(), _Plan()
+        adam.add("vp_latent_adam_f32", P(self.z), P(q.dz), P(q.m), P(q.v), P(q.step), self.B, self.Z, *hyper, P(q.prior))
+        prior.add("vp_latent_adam_f32", P(self.z), None, None, None, None, self.B, self.Z, 0.0, 0.0, 0.0, 0.0, hyper[4], P(q.prior))
+        self._plans["project"] = (p_dec, q.p_bce, q.walk, adam)
+        self._plans["project.grad"] = (p_dec, q.p_bce, q.walk, prior)
+        self._plans["project.loss"] = (p_dec, q.p_bce, prior)
+        q.hyper = hyper
+        if self._graphs:
+            self._graphs.update(self._capture([w for w in self._plans if w.startswith("project")]))
+
+    def _project_load(self, x: torch.Tensor, mask: Optional[torch.Tensor], i0: int, m: int) -> None:
+        """target and mask of one chunk into the plan's buffers; the zero rows of a short chunk get a zero mask (no loss, no gradient)"""
+        q = self._proj
+        self._load(self.x_nchw, x[i0:i0 + m])
+        if mask is None:
+            q.mask[:m].fill_(1.0)
+            q.mask[m:].zero_()
+        else:
+            self._load(q.mask, mask[i0:i0 + m])
+        if "project.load" in self._plans:
+            self._run("project.load")
+
+    def _project_args(self, x, mask, prior_weight):
+        self._check(x, "x", (self.C, self.S, self.S))
+        if mask is not None:
+            self._check(mask, "mask", (self.C, self.S, self.S))
+            if mask.shape[0] != x.shape[0]:
+                raise _lib.VaePlayHipError(f"FusedVAEInference: mask has {mask.shape[0]} rows, x has {x.shape[0]}")
+        if not prior_weight >= 0.0:
+            raise ValueError("prior_weight must be non-negative")
+
+    def decode_grad(self, z: torch.Tensor, x: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                    prior_weight: float = 0.0) -> Dict[str, torch.Tensor]:
+        """The projection objective at latents z (n, Z) for images x (n, C, S, S) and its gradient; nothing is updated:
+          x_tilde (n, C, S, S)  decode(z)
+          bce     (n,)          sum over the image of mask * per-pixel BCE(x_tilde, x)   (``mask``: fp32, the shape of x, weights in
+                                [0, 1]; None: all ones)
+          loss    (n,)          bce + prior_weight / 2 |z|^2
+          dz      (n, Z)        d loss / d z through the frozen decoder in eval mode
+        No counterpart in the reference (new functionality).  Needs a "bf16x3" or "f32" plan."""
+        self._check(z, "z", (self.Z,))
+        self._project_args(x, mask, prior_weight)
+        if x.shape[0] != z.shape[0]:
+            raise _lib.VaePlayHipError(f"FusedVAEInference: x has {x.shape[0]} rows, z has {z.shape[0]}")
+        self.enable_projection()
+        lr, b1, b2, eps, _ = self._proj.hyper
+        self._project_lists(lr, b1, b2, eps, prior_weight)
+        q, n = self._proj, z.shape[0]
+        out = {"x_tilde": x.new_empty((n, self.C, self.S, self.S)), "bce": x.new_empty((n,)), "loss": x.new_empty((n,)),
+               "dz": z.new_empty((n, self.Z))}
+        for i0, m in self._chunks(n):
+            self._load(self.z, z[i0:i0 + m])
+            self._project_load(x, mask, i0, m)
+            self._run("project.grad")
+            out["x_tilde"][i0:i0 + m].copy_(self.x_tilde[:m])
+            out["bce"][i0:i0 + m].copy_(q.bce[:m])
+            out["loss"][i0:i0 + m].copy_((q.bce + q.prior)[:m])
+            out["dz"][i0:i0 + m].copy_(q.dz[:m] if prior_weight == 0.0 else q.dz[:m] + prior_weight * self.z[:m])
+        return out
+
+    def project(self, x: torch.Tensor, steps: int = 100, lr: float = 0.05, mask: Optional[torch.Tensor] = None, z0="encode",
+                prior_weight: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8, history: bool = False) -> Dict[str, torch.Tensor]:
+        """Search the latent space for images x (n, C, S, S): ``steps`` iterations of Adam (torch.optim.Adam's update, no amsgrad, no
+        weight decay) on   loss(z) = sum over the image of mask * BCE(decode(z), x) + prior_weight / 2 |z|^2   per image, from
+        ``z0``: "encode" (the encoder mean of x), "zeros", or an (n, Z) tensor.  ``mask``: fp32, the shape of x, weights in [0, 1]
+        (inpainting, occlusion-robust scoring); None: all ones.  Returns
+          z (n, Z), x_tilde (n, C, S, S), loss (n,)   at the final z
+          history (steps, n)   with ``history=True``: the loss at the z each iteration started from
+        One iteration is ONE launch list (the decode list, the masked BCE, the input-gradient walk, the latent update) replayed
+        ``steps`` times -- as a hipGraph after ``capture()``, with the same bits: Adam's step count lives in device memory.  Rows are
+        independent (eval-mode decoder, elementwise Adam).  Every call starts from step 1 with zero moments.
+        No counterpart in the reference (new functionality).  Needs a "bf16x3" or "f32" plan."""
+        self._project_args(x, mask, prior_weight)
+        n, steps = x.shape[0], int(steps)
+        if steps < 0:
+            raise ValueError("steps must not be negative")
+        if isinstance(z0, torch.Tensor):
+            self._check(z0, "z0", (self.Z,))
+            if z0.shape[0] != n:
+                raise _lib.VaePlayHipError(f"FusedVAEInference: z0 has {z0.shape[0]} rows, x has {n}")
+        elif z0 not in ("encode", "zeros"):
+            raise ValueError("z0 must be 'encode', 'zeros' or an (n, Z) tensor")
+        self.enable_projection()
+        self._project_lists(lr, betas[0], betas[1], eps, prior_weight)
+        q = self._proj
+        out = {"z": x.new_empty((n, self.Z)), "x_tilde": x.new_empty((n, self.C, self.S, self.S)), "loss": x.new_empty((n,))}
+        if history:
+            out["history"] = x.new_empty((steps, n))
+        for i0, m in self._chunks(n):
+            self._project_load(x, mask, i0, m)
+            if isinstance(z0, torch.Tensor):
+                self._load(self.z, z0[i0:i0 + m])
+            elif z0 == "encode":
+                self._run("encode")
+                self.z.copy_(self.mu)
+            else:
+                self.z.zero_()
+            q.m.zero_()
+            q.v.zero_()
+            q.step.zero_()
+            for it in range(steps):
+                self._run("project")
+                if history:
+                    out["history"][it, i0:i0 + m].copy_((q.bce + q.prior)[:m])
+            self._run("project.loss")
+            out["z"][i0:i0 + m].copy_(self.z[:m])
+            out["x_tilde"][i0:i0 + m].copy_(self.x_tilde[:m])
+            out["loss"][i0:i0 + m].copy_((q.bce + q.prior)[:m])
+        return out
 
     def sample(self, n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
         """x_p (n, C, S, S): decode z_p ~ N(0, I) (the reference's ``x is None`` branch)"""

@@ -441,6 +441,34 @@ def iw_bound(nbce, lr, want_logw: bool = True):
     return logw, iwae
 
 
+def bce_masked_rows_bwd(p, t, mask: Optional[torch.Tensor] = None):
+    """(out, dlogit): out[r] = the mask-weighted BCE sum over row r of p, t (rows, ...), dlogit = mask * (p - t); mask None: all ones"""
+    assert _same_layout(p, t) and (mask is None or _same_layout(p, mask))
+    if not (p.is_contiguous() or _is_nhwc(p)):
+        p, t, mask = p.contiguous(), t.contiguous(), None if mask is None else mask.contiguous()
+    rows, n = p.shape[0], p.numel() // p.shape[0]
+    ws = _ws(_lib.load().vp_bce_masked_rows_bwd_workspace_bytes(rows, n), p)
+    out = torch.empty((rows,), dtype=torch.float32, device=p.device)
+    dl = torch.empty_like(p)
+    _lib.call("vp_bce_masked_rows_bwd_f32", _p(p), _p(t), _p(mask), rows, n, _p(out), _p(dl), _p(ws), ws.numel() * 4, _stream())
+    return out, dl
+
+
+def affine_relu_bwd(dy, u, scale, want_f32: bool = True, want_split: bool = False, inplace: bool = False):
+    """(dx, dx_split) = backward through u = relu(scale * c + shift) from the output: dy * scale * (u > 0) over [R][C] with
+    C = scale.numel().  ``u``: fp32, or (2, n) int16 split planes.  ``inplace``: dx is dy itself."""
+    C = scale.numel()
+    n = dy.numel()
+    assert n % C == 0 and dy.is_contiguous() and u.is_contiguous() and (want_f32 or want_split)
+    split_in = u.dtype == torch.int16
+    assert u.numel() == (2 * n if split_in else n)
+    dx = (dy if inplace else torch.empty_like(dy)) if want_f32 else None
+    dxs = empty_split(n, dy) if want_split else None
+    _lib.call("vp_affine_relu_bwd_f32", _p(dy), None if split_in else _p(u), _pv(u) if split_in else None, _p(scale), _p(dx),
+              _pv(dxs), n // C, C, _stream())
+    return dx, dxs
+
+
 def bce_bwd(p, t, g: Optional[torch.Tensor], gscale: float = 1.0):
     assert _same_layout(p, t)
     dp = torch.empty_like(p)
@@ -683,6 +711,28 @@ def adam_outer_step(p2d, m2d, v2d, A, Bm, lr, beta1, beta2, eps, step: int, grad
 
 def rmsprop_step(p, g, sq, lr, alpha, eps, grad_scale: float = 1.0):
     _lib.call("vp_rmsprop_f32", _p(p), _p(g), _p(sq), p.numel(), float(lr), float(alpha), float(eps), float(grad_scale), _stream())
+
+
+def latent_adam_step(z, g, m, v, step_count, lr, beta1, beta2, eps, prior_weight: float = 0.0, want_prior: bool = False):
+    """One Adam step on latents z (rows, Z), in place, with gradient g + prior_weight * z; ``step_count``: int32 tensor of one
+    element ON THE DEVICE holding the steps taken so far (read by the kernel, advanced by one behind it).  Returns
+    prior[r] = prior_weight / 2 |z_r|^2 of the z it read, when asked."""
+    rows, Z = z.shape
+    assert z.is_contiguous() and all(t.is_contiguous() and t.shape == z.shape for t in (g, m, v))
+    assert step_count.dtype == torch.int32 and step_count.is_cuda and step_count.numel() == 1
+    prior = torch.empty((rows,), dtype=torch.float32, device=z.device) if want_prior else None
+    _lib.call("vp_latent_adam_f32", _p(z), _p(g), _p(m), _p(v), _pv(step_count), rows, Z, float(lr), float(beta1), float(beta2),
+              float(eps), float(prior_weight), _p(prior), _stream())
+    return prior
+
+
+def latent_prior(z, prior_weight: float):
+    """prior[r] = prior_weight / 2 |z_r|^2, summed as latent_adam_step sums it (the same bits)"""
+    rows, Z = z.shape
+    assert z.is_contiguous()
+    prior = torch.empty((rows,), dtype=torch.float32, device=z.device)
+    _lib.call("vp_latent_adam_f32", _p(z), None, None, None, None, rows, Z, 0.0, 0.0, 0.0, 0.0, float(prior_weight), _p(prior), _stream())
+    return prior
 
 
 # ---- split-bf16 ("bf16x3") operands ----------------------------------------------------------------

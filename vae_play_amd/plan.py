@@ -435,16 +435,17 @@ class PlanBuilder:
                      side=k, side_args={3 + len(geom): self.wgrad_cus}, **kw)
 
     # ---- the end of a plan ----
-    def finish(self, fwd: _Plan):
+    def finish(self, fwd: _Plan, prefix: str = ""):
         """batched weight re-pack at the head of the forward plan, the dense layers' workspace; sets the step's
-        ``_n_side_events``"""
+        ``_n_side_events``.  ``prefix``: of a builder that extends a finished plan (its workspace's name, its array of pack jobs)"""
         step = self.step
-        step._pack_jobs = (_lib.PackJob * len(self._pack_jobs))(*self._pack_jobs)   # host array read by every call: keep it alive
-        fwd.add_first("vp_pack_w5_batch", step._pack_jobs, len(self._pack_jobs), side=self.k_pack)
+        jobs = (_lib.PackJob * len(self._pack_jobs))(*self._pack_jobs)
+        setattr(step, f"_{prefix.replace('.', '_')}pack_jobs", jobs)                 # host array read by every call: keep it alive
+        fwd.add_first("vp_pack_w5_batch", jobs, len(self._pack_jobs), side=self.k_pack)
         if self._first_pack_jobs:
             step._pack_jobs0 = (_lib.PackJob * len(self._first_pack_jobs))(*self._first_pack_jobs)
             fwd.add_first("vp_pack_w5_batch", step._pack_jobs0, len(self._first_pack_jobs))
-        wsg = self.ws("gemm.ws", self._gemm_need)
+        wsg = self.ws(f"{prefix}gemm.ws", self._gemm_need)
         for a in self._gemm_calls:
             a[13], a[14] = _ptr(wsg), wsg.numel() * 4
         step._n_side_events = self.n_side

@@ -221,9 +221,27 @@ class ScatterBlock:
                                    conv=(1, self.arith, self.src, self.p1, self.geom, self.fl))
 
     def fwd_eval(self, plan: _Plan, prep: _Plan):
-        folded = self.b.bn_fold(prep, self.tag, self.bn)
+        self.folded = folded = self.b.bn_fold(prep, self.tag, self.bn)
         self.fused = self.b.conv5_bn_eval(plan, self.tag, 1, self.arith, self.src, self.p1, self.geom, self.bn, folded, self.u, self.u_s,
                                           flops=self.fl, out_fmt=self.out_fmt)
+
+    def bwd_eval(self, plan: _Plan, cur, other, g_s, p0):
+        """input gradient alone, after ``fwd_eval``: dy in ``cur`` (fp32 NHWC) -> dx in ``cur``.  The block kept its output u = relu(s c + t)
+        only, so d c = dy * s * (u > 0) from the folded scale (csrc/project.hip), then the input-gradient convolution over ``p0``
+        (the gather-family pack, which the eval plan does not own).  The same for fused and unfused blocks: both leave the same
+        output.  ``g_s``: split gradient plane, ``other``: scratch of the fp32 form."""
+        b = self.b
+        geom = (self.Bn, self.Hs, self.Hs, self.Cout, self.Cin, 2)
+        scale = self.folded[0]
+        if self.is16:
+            g = g_s
+            plan.add("vp_affine_relu_bwd_f32", P(cur), P(self.u), P(self.u_s), P(scale), None, P(g_s), self.R, self.Cout,
+                     tag=f"{self.tag}.dact")
+        else:
+            g = other
+            plan.add("vp_affine_relu_bwd_f32", P(cur), P(self.u), P(self.u_s), P(scale), P(other), None, self.R, self.Cout,
+                     tag=f"{self.tag}.dact")
+        b.conv5(plan, 0, self.arith, g, p0, cur, geom, products=2, alpha=1.0 / b.GS, flops=self.fl, tag=f"{self.tag}.dgrad")
 
     def bwd(self, plan: _Plan, cur, other, gfn=grad_of):
         """dy in ``cur`` -> dx in ``cur``; ``gfn``: where a parameter's gradient lives (the shadow arena of a second pass)"""
@@ -352,13 +370,19 @@ class FinalConv:
             ws = b.ws(f"{tag}.wgrad.ws", b.lib.vp_conv5_wgrad_workspace_bytes(Bn, S, S, Cf, C, 1)) if self.own_wgrad_ws else b.ws_wg
             plan.add("vp_conv5_wgrad_f32", P(src), P(dlogit), P(dw), Bn, S, S, Cf, C, 1, P(ws), ws.numel() * 4,
                      flops=self.fl, tag=f"{tag}.wgrad", side=b.side_slot())
+        self.dgrad(plan, tag, dlogit, out)
+
+    def dgrad(self, plan: _Plan, tag: str, dlogit, out, p1=None):
+        """the input gradient alone (into ``out``): no weight or bias gradient, no side stream.  ``p1``: the scatter-family pack of
+        the generic route where the object owns none (an eval plan)"""
+        b, Bn, S, Cf, C = self.b, self.Bn, self.S, self.Cf, self.C
         if self.edge:       # rows-in-K tiling, split-bf16 or exact fp32 (csrc/edge.hip)
             plan.add("vp_conv5_smallin_dgrad_bf16x3" if b.x3 else "vp_conv5_smallin_dgrad_f32", P(dlogit), P(self.conv.weight), P(out),
                      Bn, S, S, C, Cf, flops=self.fl, tag=f"{tag}.dgrad")
         elif self.halo:
             b.conv5(plan, 1, "bf16x3", self.dlogit_s, self.p1s, out, (Bn, S, S, 8, Cf, 1), flops=self.fl, tag=f"{tag}.dgrad")
         else:
-            b.conv5(plan, 1, "f32", dlogit, self.p1, out, (Bn, S, S, C, Cf, 1), flops=self.fl, tag=f"{tag}.dgrad")
+            b.conv5(plan, 1, "f32", dlogit, self.p1 if p1 is None else p1, out, (Bn, S, S, C, Cf, 1), flops=self.fl, tag=f"{tag}.dgrad")
 
 
 # ---- decoder trunk -----------------------------------------------------------------------------------------------------------
@@ -387,7 +411,8 @@ class DecoderTrunk:
         if self.train:
             ps.fc_saved = b.bn_fwd(plan, f"{tag}.fc", ps.d, Bn, F1, self.fc_bn, ps.db)
         else:
-            b.bn_eval(plan, f"{tag}.fc", ps.d, Bn, F1, self.fc_bn, b.bn_fold(prep, f"{tag}.fc", self.fc_bn)[2], ps.db)
+            ps.fc_folded = b.bn_fold(prep, f"{tag}.fc", self.fc_bn)
+            b.bn_eval(plan, f"{tag}.fc", ps.d, Bn, F1, self.fc_bn, ps.fc_folded[2], ps.db)
         src, src_s = _outputs(b, f"{tag}.in", Bn * F1, self.packs[0][2])
         if b.fp16:
             plan.add("vp_nchw_to_nhwc_split_fmt_f32", P(ps.db), P(src), P(src_s), Bn, self.size, 8, 8, ops.SPLIT_F16)
@@ -420,3 +445,16 @@ class DecoderTrunk:
         b.lin_wgrad(plan, cur, ps.z, gfn(self.fc_lin.weight), Bn, F1, self.Z)
         if dz is not None:
             b.lin_dgrad(plan, cur, self.fc_lin.weight, dz, Bn, F1, self.Z)
+
+    def bwd_eval(self, plan: _Plan, b: PlanBuilder, ps: SimpleNamespace, dlogit, cur, other, g_s, p0s, dz, fin_p1=None):
+        """input gradients alone through an eval-form pass ``ps``: ``dlogit`` -> d z in ``dz``.  ``b``: the builder the dense input gradient's
+        workspace is sized by (the caller's, which also owns the fp32 ping-pong ``cur`` / ``other``, the split gradient plane ``g_s``
+        and ``p0s``, the blocks' gather-family packs)"""
+        Bn, F1 = self.Bn, self.F1
+        self.fin.dgrad(plan, ps.fin_tag, dlogit, cur, fin_p1)
+        for blk, p0 in zip(reversed(ps.blocks), reversed(p0s)):
+            blk.bwd_eval(plan, cur, other, g_s, p0)
+        plan.add("vp_nhwc_to_nchw_f32", P(cur), P(other), Bn, self.size, 8, 8)                  # other = d db  (Bn, F1)
+        plan.add("vp_affine_relu_bwd_f32", P(other), P(ps.db), None, P(ps.fc_folded[0]), P(cur), None, Bn, F1,
+                 tag=f"{ps.tag}.fc.dact")                                                       # cur = d d
+        b.lin_dgrad(plan, cur, self.fc_lin.weight, dz, Bn, F1, self.Z)

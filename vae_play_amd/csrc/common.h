@@ -75,5 +75,57 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
   return v;
 }
+__device__ __forceinline__ double wave_sum(double v) { return wave_sum_d(v); }
+
+// Sum over a 256-thread workgroup (four waves), returned to every thread: the wave tree, then (sh[0] + sh[1]) + (sh[2] + sh[3]).
+// sh holds four values; a kernel with several accumulators calls this once per accumulator, each with four values of its own.
+// The one fixed order of every block sum of the small kernels (elementwise.hip, score.h).  The serial sums of
+// cross_entropy_fwd_kernel (256 entries), l1_final_kernel and be_loss_final_kernel have other orders and stay as they are.
+template <class T>
+__device__ __forceinline__ T block_sum4(T lane_value, T* sh) {
+  const T w = wave_sum(lane_value);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
+  __syncthreads();
+  return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+// ---- loss terms stated once -------------------------------------------------------------------------------------------------------
+// F.binary_cross_entropy's term t log p + (1 - t) log(1 - p) with torch's clamp of each logarithm at -100; the callers subtract it
+// (reduce_partial_kernel<0> of elementwise.hip, bce_rows_kernel of score.h)
+__device__ __forceinline__ float bce_term(float p, float t) {
+  const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.f - p), -100.f);
+  return t * lp + (1.f - t) * lq;
+}
+
+// p = sigmoid(x) and q = 1 - p = sigmoid(-x), each from e = exp(-|x|), which the caller computes (expf in the GAN head, __expf in
+// the BE kernels): "1.f - p" loses q once p rounds towards 1
+__device__ __forceinline__ void sigmoid_pair(float x, float e, float& p, float& q) {
+  const float big = 1.f / (1.f + e), small = e / (1.f + e);
+  p = x >= 0.f ? big : small;
+  q = x >= 0.f ? small : big;
+}
+
+// ---- host launch sequences stated once ---------------------------------------------------------------------------------------------
+// a flat kernel of 256-thread workgroups over `items` work items, its grid capped at `cap` workgroups (grid_for)
+constexpr unsigned FLAT_CAP = 256 * 8;
+template <class... K, class... A>
+inline int launch_flat(const char* what, void (*kernel)(K...), size_t items, unsigned cap, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid_for(items, 256, cap)), dim3(256), 0, s, static_cast<K>(args)...);
+  return check_launch(what);
+}
+
+// the two-stage reductions: the workspace check with the caller's message, the partial launch, the final launch
+template <class Partial, class Final>
+inline int two_stage(const char* what, bool ws_ok, const char* ws_message, Partial partial, Final final) {
+  if (!ws_ok) return fail(VP_ERR_WORKSPACE, "%s: %s", what, ws_message);
+  auto check = [what](const char* stage) {
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? (int)VP_OK : fail(VP_ERR_LAUNCH, "%s(%s): %s", what, stage, hipGetErrorString(e));
+  };
+  partial();
+  if (int rc = check("partial")) return rc;
+  final();
+  return check("final");
+}
 
 }  // namespace vp

@@ -1,6 +1,5 @@
 // HBM-bound glue kernels: layout transposes, latent (reparameterise + KL), per-pixel BCE with
-// wavefront reductions, and the fused flat-arena optimiser steps.
-#include <stdlib.h>
+// wavefront reductions, the loss heads and the pointwise helpers of models/blocks.py.  The flat optimisers are optim.hip's.
 #include "common.h"
 #include "problems.h"
 #include "split.h"
@@ -99,27 +98,18 @@ __global__ void __launch_bounds__(256) reduce_partial_kernel(const float* __rest
     if (MODE == 0) {
       vp_f32x4 tv = *reinterpret_cast<const vp_f32x4*>(t + i * 4);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float lp = fmaxf(logf(pv[j]), -100.f), lq = fmaxf(logf(1.f - pv[j]), -100.f);
-        acc -= tv[j] * lp + (1.f - tv[j]) * lq;
-      }
+      for (int j = 0; j < 4; ++j) acc -= bce_term(pv[j], tv[j]);
     } else {
       acc += (pv[0] + pv[1]) + (pv[2] + pv[3]);
     }
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail
     const size_t i = n4 * 4 + threadIdx.x;
-    if (MODE == 0) {
-      const float lp = fmaxf(logf(p[i]), -100.f), lq = fmaxf(logf(1.f - p[i]), -100.f);
-      acc -= t[i] * lp + (1.f - t[i]) * lq;
-    } else {
-      acc += p[i];
-    }
+    if (MODE == 0) acc -= bce_term(p[i], t[i]);
+    else acc += p[i];
   }
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  acc = block_sum4(acc, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = acc;
 }
 
 __global__ void reduce_final_kernel(const float* __restrict__ part, int nblocks, float* __restrict__ out) {
@@ -173,10 +163,8 @@ __global__ void __launch_bounds__(256) half_sqdiff_rowsum_kernel(const float* __
     s1 += 0.5f * d1 * d1;
   }
   if (j < n) { const float d0 = a[base + j] - b[base + j]; s0 += 0.5f * d0 * d0; }
-  const double w = wave_sum_d((double)s0 + (double)s1);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) out[blockIdx.x] = (float)((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  const double w = block_sum4((double)s0 + (double)s1, sh);
+  if (threadIdx.x == 0) out[blockIdx.x] = (float)w;
 }
 
 // da = g * (a - b), db = -da with g per element (per_row = 0) or per row (per_row = 1)
@@ -199,12 +187,11 @@ __global__ void __launch_bounds__(256) gan_head_kernel(const float* __restrict__
   __shared__ float sh[3][4];
   float acc[3] = {0.f, 0.f, 0.f};
   for (int i = threadIdx.x; i < 3 * B; i += 256) {
-    // y = sigmoid(x) and q = 1 - y = sigmoid(-x), each from e = exp(-|x|): "1.f - y" loses q once y rounds towards 1 (|q| error
-    // 6e-8 against the 1e-3 floor: 6e-5 of dlogit, and a saturated logit got gradient 0 instead of coef * 1e3 * q)
+    // q from sigmoid_pair, not "1.f - y": that error is 6e-8 against the 1e-3 floor, 6e-5 of dlogit, and a saturated logit got
+    // gradient 0 instead of coef * 1e3 * q
     const float x = logit[i];
-    const float e = expf(-fabsf(x));
-    const float big = 1.f / (1.f + e), small = e / (1.f + e);
-    const float y = x >= 0.f ? big : small, q = x >= 0.f ? small : big;
+    float y, q;
+    sigmoid_pair(x, expf(-fabsf(x)), y, q);
     const int grp = i / B;
     float u, dldy;
     if (grp == 0) { u = y + 1e-3f; dldy = -1.f / u; }
@@ -215,11 +202,9 @@ __global__ void __launch_bounds__(256) gan_head_kernel(const float* __restrict__
   }
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
-    const float w = wave_sum(acc[g]);
-    if ((threadIdx.x & 63) == 0) sh[g][threadIdx.x >> 6] = w;
+    const float w = block_sum4(acc[g], sh[g]);
+    if (threadIdx.x == 0 && sums) sums[g] = w;
   }
-  __syncthreads();
-  if (threadIdx.x < 3 && sums) sums[threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
 }
 
 // F.smooth_l1_loss(targets, cat(a, b), reduction="sum") * scale (models/networks.py:279: beta = 1) over B rows of n1 + n2 columns;
@@ -239,10 +224,8 @@ __global__ void __launch_bounds__(256) smooth_l1_cat_kernel(const float* __restr
     if (c < n1) { if (da) da[r * n1 + c] = g; }
     else if (db) db[r * n2 + (c - n1)] = g;
   }
-  const float w = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0 && loss) loss[0] = scale * ((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  const float w = block_sum4(acc, sh);
+  if (threadIdx.x == 0 && loss) loss[0] = scale * w;
 }
 
 // ---- segmentation loss of train_BE.py:58-59: w * BCEWithLogits(x, t) (mean) + dice(sigmoid(x), t) (tools/ops.py:12-19)
@@ -264,7 +247,8 @@ __global__ void __launch_bounds__(256) be_loss_partial_kernel(const float* __res
     float p = xv;
     if constexpr (!PROBS) {
       const float e = __expf(-fabsf(xv));
-      p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+      float q;
+      sigmoid_pair(xv, e, p, q);
       s[0] += fmaxf(xv, 0.f) - xv * tv + log1pf(e);
     }
     s[1] += p * tv;
@@ -273,13 +257,8 @@ __global__ void __launch_bounds__(256) be_loss_partial_kernel(const float* __res
   }
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
-    const double w = wave_sum_d((double)s[k]);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = w;
-  }
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int k = threadIdx.x;
-    part[((size_t)b * nchunk + c) * 4 + k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
+    const double w = block_sum4((double)s[k], sh[k]);
+    if (threadIdx.x == 0) part[((size_t)b * nchunk + c) * 4 + k] = w;
   }
 }
 
@@ -318,11 +297,35 @@ __global__ void be_loss_bwd_kernel(const float* __restrict__ x, const float* __r
     if constexpr (PROBS) {
       dx[base + i] = ab * tv + bb;
     } else {
-      const float e = __expf(-fabsf(xv));
-      const float p = xv >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-      dx[base + i] = cb * (p - tv) + (ab * tv + bb) * p * (1.f - p);
+      float p, q;
+      sigmoid_pair(xv, __expf(-fabsf(xv)), p, q);
+      dx[base + i] = cb * (p - tv) + (ab * tv + bb) * p * (1.f - p);     // ("1.f - p", not q: the bits this kernel always wrote)
     }
   }
+}
+
+// the host side of the BE loss (PROBS = false: logits, BCE + dice) and of the plain dice loss (PROBS = true: bce_weight 0)
+template <bool PROBS>
+inline int be_loss_fwd(const char* what, const float* x, const float* targets, float* loss, float* sums, int B, int n, float bce_weight,
+                       float smooth, void* ws, size_t ws_bytes, vp_stream stream) {
+  VP_REQUIRE(x && targets && loss && sums && ws && B > 0 && n > 0, "%s: bad arguments", what);
+  const int nchunk = (n + BE_CHUNK - 1) / BE_CHUNK;
+  hipStream_t s = (hipStream_t)stream;
+  return two_stage(
+      what, ws_bytes >= (size_t)B * nchunk * 4 * sizeof(double), "workspace too small",
+      [&] { hipLaunchKernelGGL((be_loss_partial_kernel<PROBS>), dim3(nchunk, B), dim3(256), 0, s, x, targets, (double*)ws, n, nchunk); },
+      [&] {
+        hipLaunchKernelGGL(be_loss_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, sums, loss, B, n, nchunk, bce_weight, smooth);
+      });
+}
+
+template <bool PROBS>
+inline int be_loss_bwd(const char* what, const float* x, const float* targets, const float* sums, const float* gptr, float* dx, int B,
+                       int n, float bce_weight, float smooth, vp_stream stream) {
+  VP_REQUIRE(x && targets && sums && dx && B > 0 && n > 0, "%s: bad arguments", what);
+  hipLaunchKernelGGL((be_loss_bwd_kernel<PROBS>), dim3(grid_for((size_t)n, 256, 256), B), dim3(256), 0, (hipStream_t)stream, x, targets,
+                     sums, gptr, dx, B, n, bce_weight, smooth);
+  return check_launch(what);
 }
 
 // ---- nn.AdaptiveAvgPool2d((1,1)) on NHWC (models/networks_BE_font.py:61): out[b][c] = mean over the HW pixels ------
@@ -380,10 +383,8 @@ __global__ void __launch_bounds__(256) l1_partial_kernel(const float* __restrict
   __shared__ double sh[4];
   float s = 0.f;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) s += fabsf(a[i] - b[i]);
-  const double w = wave_sum_d((double)s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  const double w = block_sum4((double)s, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = w;
 }
 
 __global__ void l1_final_kernel(const double* __restrict__ part, int nb, size_t n, float* __restrict__ out) {
@@ -535,153 +536,39 @@ __global__ void slice_channels_kernel(const float* __restrict__ in, float* __res
   }
 }
 
-// torch.optim.Adam (single-tensor form): m.lerp_(g, 1-b1); v = v*b2 + (1-b2)*g*g;
-// denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) * m/denom
-__global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, size_t n, float one_minus_b1, float b2,
-                                                   float one_minus_b2, float eps, float step_size, float bc2_sqrt,
-                                                   float grad_scale) {
-  const size_t n4 = n / 4;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  auto upd = [&](vp_f32x4& pv, const vp_f32x4& gv, vp_f32x4& mv, vp_f32x4& vv) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float gr = gv[j] * grad_scale;
-      mv[j] = mv[j] + one_minus_b1 * (gr - mv[j]);
-      vv[j] = vv[j] * b2 + one_minus_b2 * gr * gr;
-      const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-      pv[j] = pv[j] - step_size * (mv[j] / denom);
-    }
-  };
-  // two independent 16-B quads per thread and iteration: 8 loads in flight before the first use; the moments
-  // are streamed with non-temporal accesses (touched once per step), p and g stay cacheable for their consumers
-  size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const size_t a = i * 4, b = (i + stride) * 4;
-    vp_f32x4 pa = *reinterpret_cast<vp_f32x4*>(p + a), pb = *reinterpret_cast<vp_f32x4*>(p + b);
-    vp_f32x4 ga = *reinterpret_cast<const vp_f32x4*>(g + a), gb = *reinterpret_cast<const vp_f32x4*>(g + b);
-    vp_f32x4 ma = __builtin_nontemporal_load(reinterpret_cast<vp_f32x4*>(m + a));
-    vp_f32x4 mb = __builtin_nontemporal_load(reinterpret_cast<vp_f32x4*>(m + b));
-    vp_f32x4 va = __builtin_nontemporal_load(reinterpret_cast<vp_f32x4*>(v + a));
-    vp_f32x4 vb = __builtin_nontemporal_load(reinterpret_cast<vp_f32x4*>(v + b));
-    upd(pa, ga, ma, va);
-    upd(pb, gb, mb, vb);
-    *reinterpret_cast<vp_f32x4*>(p + a) = pa;
-    *reinterpret_cast<vp_f32x4*>(p + b) = pb;
-    __builtin_nontemporal_store(ma, reinterpret_cast<vp_f32x4*>(m + a));
-    __builtin_nontemporal_store(mb, reinterpret_cast<vp_f32x4*>(m + b));
-    __builtin_nontemporal_store(va, reinterpret_cast<vp_f32x4*>(v + a));
-    __builtin_nontemporal_store(vb, reinterpret_cast<vp_f32x4*>(v + b));
+// ---- F.cross_entropy(logits, labels) (mean over rows): train_BE_GAN.py:135,159, train_BE_font.py:109 ---------------------------
+// R rows of n logits, labels int64.  One workgroup; a thread owns whole rows (R = batch size, n = a handful of classes), the row
+// losses are summed in a fixed order: bit-reproducible.  prob[r][j] = softmax (kept for the backward pass).
+__global__ void __launch_bounds__(256) cross_entropy_fwd_kernel(const float* __restrict__ x, const long long* __restrict__ labels,
+                                                                float* __restrict__ loss, float* __restrict__ prob, int R, int n) {
+  __shared__ double part[256];
+  double acc = 0.0;
+  for (int r = threadIdx.x; r < R; r += 256) {
+    const float* xr = x + (size_t)r * n;
+    float m = xr[0];
+    for (int j = 1; j < n; ++j) m = fmaxf(m, xr[j]);
+    float ssum = 0.f;
+    for (int j = 0; j < n; ++j) ssum += __builtin_expf(xr[j] - m);
+    const float inv = 1.f / ssum;
+    for (int j = 0; j < n; ++j) prob[(size_t)r * n + j] = __builtin_expf(xr[j] - m) * inv;
+    const long long lb = labels[r];
+    const float xl = (lb >= 0 && lb < n) ? xr[lb] : 0.f;          // (an out-of-range label contributes lse only; the host checks)
+    acc += (double)((m + __builtin_logf(ssum)) - xl);
   }
-  if (i < n4) {
-    const size_t a = i * 4;
-    vp_f32x4 pa = *reinterpret_cast<vp_f32x4*>(p + a);
-    vp_f32x4 ga = *reinterpret_cast<const vp_f32x4*>(g + a);
-    vp_f32x4 ma = *reinterpret_cast<vp_f32x4*>(m + a), va = *reinterpret_cast<vp_f32x4*>(v + a);
-    upd(pa, ga, ma, va);
-    *reinterpret_cast<vp_f32x4*>(p + a) = pa;
-    *reinterpret_cast<vp_f32x4*>(m + a) = ma;
-    *reinterpret_cast<vp_f32x4*>(v + a) = va;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const size_t i = n4 * 4 + threadIdx.x;
-    const float gr = g[i] * grad_scale;
-    const float mm = m[i] + one_minus_b1 * (gr - m[i]);
-    const float vv = v[i] * b2 + one_minus_b2 * gr * gr;
-    m[i] = mm; v[i] = vv;
-    p[i] = p[i] - step_size * (mm / (sqrtf(vv) / bc2_sqrt + eps));
+  part[threadIdx.x] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < 256; ++i) t += part[i];
+    loss[0] = (float)(t / (double)R);
   }
 }
-
-// Adam update of a weight matrix p[R][Cn] whose gradient is a sum of K outer products, g = grad_scale * A^T B with A [K][R] and
-// B [K][Cn] (a Linear layer's weight gradient: A = the output gradients, B = the inputs of the K samples).  The gradient is
-// contracted in registers and consumed at once: for the encoder's first dense layer (1024 x 32768, 63 % of the model's parameters,
-// K = 32 images) that saves writing and re-reading a 134-MB gradient matrix per step.  One workgroup = 16 rows x 1024 columns,
-// one thread = 16 rows x 4 columns (64 accumulators); per k it loads one 16-B quad of B and 16 wave-uniform values of A.
-template <int AO_TI>
-__global__ void __launch_bounds__(256) adam_outer_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
-                                                         const float* __restrict__ A, const float* __restrict__ Bm, int K, int R, int Cn,
-                                                         float one_minus_b1, float b2, float one_minus_b2, float eps, float step_size,
-                                                         float bc2_sqrt, float grad_scale) {
-  const int j = (blockIdx.x * 256 + threadIdx.x) * 4;
-  const int i0 = blockIdx.y * AO_TI;
-  if (j >= Cn) return;
-  float acc[AO_TI][4];
-#pragma unroll
-  for (int i = 0; i < AO_TI; ++i)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) acc[i][c] = 0.f;
-  const bool full = i0 + AO_TI <= R;
-  auto kstep = [&](int k) {
-    const vp_f32x4 b4 = *reinterpret_cast<const vp_f32x4*>(Bm + (size_t)k * Cn + j);
-    const float* ak = A + (size_t)k * R + i0;
-    float a[AO_TI];
-    if (full) {
-#pragma unroll
-      for (int q = 0; q < AO_TI / 4; ++q) {
-        const vp_f32x4 t = *reinterpret_cast<const vp_f32x4*>(ak + 4 * q);
-        a[4 * q] = t[0]; a[4 * q + 1] = t[1]; a[4 * q + 2] = t[2]; a[4 * q + 3] = t[3];
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < AO_TI; ++i) a[i] = i0 + i < R ? ak[i] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < AO_TI; ++i)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) acc[i][c] = fmaf(a[i], b4[c], acc[i][c]);
-  };
-  int k = 0;
-  for (; k + 4 <= K; k += 4) {      // four k per trip: their loads are issued together
-    kstep(k); kstep(k + 1); kstep(k + 2); kstep(k + 3);
-  }
-  for (; k < K; ++k) kstep(k);
-  auto upd = [&](vp_f32x4& pv, vp_f32x4& mv, vp_f32x4& vv, const float (&g4)[4]) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const float gr = g4[c] * grad_scale;
-      mv[c] = mv[c] + one_minus_b1 * (gr - mv[c]);
-      vv[c] = vv[c] * b2 + one_minus_b2 * gr * gr;
-      const float denom = sqrtf(vv[c]) / bc2_sqrt + eps;
-      pv[c] = pv[c] - step_size * (mv[c] / denom);
-    }
-  };
-  // rows in groups of four: 12 independent 16-B loads in flight before the first use (every row index is a compile-time
-  // constant: a runtime index would send the accumulators to scratch)
-#pragma unroll
-  for (int i4 = 0; i4 < AO_TI; i4 += 4) {
-    vp_f32x4 pv[4], mv[4], vv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r = i0 + i4 + u;
-      const size_t o = (size_t)(r < R ? r : R - 1) * Cn + j;         // (rows past the end: clamped load, no store)
-      pv[u] = *reinterpret_cast<vp_f32x4*>(p + o);
-      mv[u] = __builtin_nontemporal_load(reinterpret_cast<vp_f32x4*>(m + o));
-      vv[u] = __builtin_nontemporal_load(reinterpret_cast<vp_f32x4*>(v + o));
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int r = i0 + i4 + u;
-      if (r >= R) continue;
-      const size_t o = (size_t)r * Cn + j;
-      upd(pv[u], mv[u], vv[u], acc[i4 + u]);
-      *reinterpret_cast<vp_f32x4*>(p + o) = pv[u];
-      __builtin_nontemporal_store(mv[u], reinterpret_cast<vp_f32x4*>(m + o));
-      __builtin_nontemporal_store(vv[u], reinterpret_cast<vp_f32x4*>(v + o));
-    }
-  }
-}
-
-
-// torch.optim.RMSprop: sq = alpha*sq + (1-alpha)*g*g; p -= lr * g / (sqrt(sq) + eps)
-__global__ void __launch_bounds__(256) rmsprop_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ sq,
-                                                      size_t n, float lr, float alpha, float one_minus_alpha, float eps,
-                                                      float grad_scale) {
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gr = g[i] * grad_scale;
-    const float s = sq[i] * alpha + one_minus_alpha * gr * gr;
-    sq[i] = s;
-    p[i] = p[i] - lr * (gr / (sqrtf(s) + eps));
+__global__ void cross_entropy_bwd_kernel(const float* __restrict__ prob, const long long* __restrict__ labels, const float* __restrict__ g,
+                                         float* __restrict__ dx, int R, int n) {
+  const float gs = g[0] / (float)R;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)R * n; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / n), j = (int)(i - (size_t)r * n);
+    dx[i] = gs * (prob[i] - (labels[r] == j ? 1.f : 0.f));
   }
 }
 
@@ -716,9 +603,8 @@ int vp_latent_fwd_f32(const float* mu, const float* logvar, const float* eps, fl
 int vp_latent_bwd_f32(const float* mu, const float* logvar, const float* eps, const float* dz, const float* gkl,
                       float gkl_scalar, float* dmu, float* dlogvar, int B, int Z, vp_stream stream) {
   VP_REQUIRE(mu && logvar && eps && dmu && dlogvar && B > 0 && Z > 0, "vp_latent_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(latent_bwd_kernel, dim3(grid_for((size_t)B * Z, 256)), dim3(256), 0, (hipStream_t)stream, mu, logvar, eps, dz,
-                     gkl, gkl_scalar, dmu, dlogvar, B, Z);
-  return check_launch("vp_latent_bwd_f32");
+  return launch_flat("vp_latent_bwd_f32", latent_bwd_kernel, (size_t)B * Z, FLAT_CAP, (hipStream_t)stream, mu, logvar, eps, dz, gkl,
+                     gkl_scalar, dmu, dlogvar, B, Z);
 }
 
 size_t vp_reduce_workspace_bytes(size_t n) { return (size_t)reduce_blocks(n) * sizeof(float); }
@@ -726,44 +612,39 @@ size_t vp_reduce_workspace_bytes(size_t n) { return (size_t)reduce_blocks(n) * s
 int vp_bce_sum_f32(const float* p, const float* t, size_t n, float* out, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(p && t && out && ws && n > 0, "vp_bce_sum_f32: bad arguments");
   const unsigned nb = reduce_blocks(n);
-  if (ws_bytes < nb * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_bce_sum_f32: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((reduce_partial_kernel<0>), dim3(nb), dim3(256), 0, s, p, t, n, (float*)ws);
-  int rc = check_launch("vp_bce_sum_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, (int)nb, out);
-  return check_launch("vp_bce_sum_f32(final)");
+  return two_stage(
+      "vp_bce_sum_f32", ws_bytes >= nb * sizeof(float), "workspace too small",
+      [&] { hipLaunchKernelGGL((reduce_partial_kernel<0>), dim3(nb), dim3(256), 0, s, p, t, n, (float*)ws); },
+      [&] { hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, (int)nb, out); });
 }
 
 int vp_vae_loss_f32(const float* x_tilde, const float* x, size_t n, const float* kl, int B, float* recon, float* kl_sum, float* loss,
                     float loss_scale, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(x_tilde && x && kl && recon && kl_sum && loss && ws && n > 0 && B > 0, "vp_vae_loss_f32: bad arguments");
   const unsigned nb = reduce_blocks(n);
-  if (ws_bytes < nb * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_vae_loss_f32: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((reduce_partial_kernel<0>), dim3(nb), dim3(256), 0, s, x_tilde, x, n, (float*)ws);
-  int rc = check_launch("vp_vae_loss_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(vae_loss_final_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, (int)nb, kl, B, recon, kl_sum, loss, loss_scale);
-  return check_launch("vp_vae_loss_f32(final)");
+  return two_stage(
+      "vp_vae_loss_f32", ws_bytes >= nb * sizeof(float), "workspace too small",
+      [&] { hipLaunchKernelGGL((reduce_partial_kernel<0>), dim3(nb), dim3(256), 0, s, x_tilde, x, n, (float*)ws); },
+      [&] {
+        hipLaunchKernelGGL(vae_loss_final_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, (int)nb, kl, B, recon, kl_sum, loss, loss_scale);
+      });
 }
 
 int vp_add_f32(const float* a, const float* b, float* out, size_t n, vp_stream stream) {
   VP_REQUIRE(a && b && out && n > 0, "vp_add_f32: bad arguments");
-  hipLaunchKernelGGL(add_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
-  return check_launch("vp_add_f32");
+  return launch_flat("vp_add_f32", add_kernel, n, FLAT_CAP, (hipStream_t)stream, a, b, out, n);
 }
 
 int vp_sum_f32(const float* x, size_t n, float* out, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(x && out && ws && n > 0, "vp_sum_f32: bad arguments");
   const unsigned nb = reduce_blocks(n);
-  if (ws_bytes < nb * sizeof(float)) return fail(VP_ERR_WORKSPACE, "vp_sum_f32: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((reduce_partial_kernel<1>), dim3(nb), dim3(256), 0, s, x, (const float*)nullptr, n, (float*)ws);
-  int rc = check_launch("vp_sum_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, (int)nb, out);
-  return check_launch("vp_sum_f32(final)");
+  return two_stage(
+      "vp_sum_f32", ws_bytes >= nb * sizeof(float), "workspace too small",
+      [&] { hipLaunchKernelGGL((reduce_partial_kernel<1>), dim3(nb), dim3(256), 0, s, x, (const float*)nullptr, n, (float*)ws); },
+      [&] { hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, s, (const float*)ws, (int)nb, out); });
 }
 
 int vp_global_avgpool_fwd_f32(const float* x_nhwc, float* out, int B, int HW, int C, vp_stream stream) {
@@ -775,8 +656,7 @@ int vp_global_avgpool_fwd_f32(const float* x_nhwc, float* out, int B, int HW, in
 int vp_global_avgpool_bwd_f32(const float* dy, float* dx_nhwc, int B, int HW, int C, vp_stream stream) {
   VP_REQUIRE(dy && dx_nhwc && B > 0 && HW > 0 && C > 0, "vp_global_avgpool_bwd_f32: bad arguments");
   const size_t total = (size_t)B * HW * C;
-  hipLaunchKernelGGL(global_avgpool_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, dx_nhwc, total, HW, C);
-  return check_launch("vp_global_avgpool_bwd_f32");
+  return launch_flat("vp_global_avgpool_bwd_f32", global_avgpool_bwd_kernel, total, FLAT_CAP, (hipStream_t)stream, dy, dx_nhwc, total, HW, C);
 }
 
 int vp_softmax_rows_fwd_f32(const float* x, float* y, int R, int n, vp_stream stream) {
@@ -794,19 +674,16 @@ int vp_softmax_rows_bwd_f32(const float* y, const float* dy, float* dx, int R, i
 int vp_l1_mean_f32(const float* a, const float* b, size_t n, float* out, void* ws, size_t ws_bytes, vp_stream stream) {
   VP_REQUIRE(a && b && out && ws && n > 0, "vp_l1_mean_f32: bad arguments");
   const unsigned nb = reduce_blocks(n);
-  if (ws_bytes < nb * sizeof(double)) return fail(VP_ERR_WORKSPACE, "vp_l1_mean_f32: workspace too small (use 2 * vp_reduce_workspace_bytes)");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(l1_partial_kernel, dim3(nb), dim3(256), 0, s, a, b, (double*)ws, n);
-  int rc = check_launch("vp_l1_mean_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, (int)nb, n, out);
-  return check_launch("vp_l1_mean_f32(final)");
+  return two_stage(
+      "vp_l1_mean_f32", ws_bytes >= nb * sizeof(double), "workspace too small (use 2 * vp_reduce_workspace_bytes)",
+      [&] { hipLaunchKernelGGL(l1_partial_kernel, dim3(nb), dim3(256), 0, s, a, b, (double*)ws, n); },
+      [&] { hipLaunchKernelGGL(l1_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, (int)nb, n, out); });
 }
 
 int vp_l1_mean_bwd_f32(const float* a, const float* b, const float* gptr, float* da, float* db, size_t n, vp_stream stream) {
   VP_REQUIRE(a && b && (da || db) && n > 0, "vp_l1_mean_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(l1_bwd_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, gptr, da, db, n);
-  return check_launch("vp_l1_mean_bwd_f32");
+  return launch_flat("vp_l1_mean_bwd_f32", l1_bwd_kernel, n, FLAT_CAP, (hipStream_t)stream, a, b, gptr, da, db, n);
 }
 
 size_t vp_be_loss_workspace_bytes(int B, int n) {
@@ -816,50 +693,24 @@ size_t vp_be_loss_workspace_bytes(int B, int n) {
 
 int vp_be_loss_fwd_f32(const float* logits, const float* targets, float* loss, float* sums, int B, int n, float bce_weight,
                        float smooth, void* ws, size_t ws_bytes, vp_stream stream) {
-  VP_REQUIRE(logits && targets && loss && sums && ws && B > 0 && n > 0, "vp_be_loss_fwd_f32: bad arguments");
-  if (ws_bytes < vp_be_loss_workspace_bytes(B, n)) return fail(VP_ERR_WORKSPACE, "vp_be_loss_fwd_f32: workspace too small");
-  const int nchunk = (n + BE_CHUNK - 1) / BE_CHUNK;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((be_loss_partial_kernel<false>), dim3(nchunk, B), dim3(256), 0, s, logits, targets, (double*)ws, n, nchunk);
-  int rc = check_launch("vp_be_loss_fwd_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(be_loss_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, sums, loss, B, n, nchunk, bce_weight, smooth);
-  return check_launch("vp_be_loss_fwd_f32(final)");
+  return be_loss_fwd<false>("vp_be_loss_fwd_f32", logits, targets, loss, sums, B, n, bce_weight, smooth, ws, ws_bytes, stream);
 }
-
 int vp_be_loss_bwd_f32(const float* logits, const float* targets, const float* sums, const float* gptr, float* dlogits, int B,
                        int n, float bce_weight, float smooth, vp_stream stream) {
-  VP_REQUIRE(logits && targets && sums && dlogits && B > 0 && n > 0, "vp_be_loss_bwd_f32: bad arguments");
-  hipLaunchKernelGGL((be_loss_bwd_kernel<false>), dim3(grid_for((size_t)n, 256, 256), B), dim3(256), 0, (hipStream_t)stream, logits,
-                     targets, sums, gptr, dlogits, B, n, bce_weight, smooth);
-  return check_launch("vp_be_loss_bwd_f32");
+  return be_loss_bwd<false>("vp_be_loss_bwd_f32", logits, targets, sums, gptr, dlogits, B, n, bce_weight, smooth, stream);
 }
-
 int vp_dice_loss_fwd_f32(const float* probs, const float* targets, float* loss, float* sums, int B, int n, float smooth, void* ws,
                          size_t ws_bytes, vp_stream stream) {
-  VP_REQUIRE(probs && targets && loss && sums && ws && B > 0 && n > 0, "vp_dice_loss_fwd_f32: bad arguments");
-  if (ws_bytes < vp_be_loss_workspace_bytes(B, n)) return fail(VP_ERR_WORKSPACE, "vp_dice_loss_fwd_f32: workspace too small");
-  const int nchunk = (n + BE_CHUNK - 1) / BE_CHUNK;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((be_loss_partial_kernel<true>), dim3(nchunk, B), dim3(256), 0, s, probs, targets, (double*)ws, n, nchunk);
-  int rc = check_launch("vp_dice_loss_fwd_f32(partial)");
-  if (rc) return rc;
-  hipLaunchKernelGGL(be_loss_final_kernel, dim3(1), dim3(64), 0, s, (const double*)ws, sums, loss, B, n, nchunk, 0.f, smooth);
-  return check_launch("vp_dice_loss_fwd_f32(final)");
+  return be_loss_fwd<true>("vp_dice_loss_fwd_f32", probs, targets, loss, sums, B, n, 0.f, smooth, ws, ws_bytes, stream);
 }
-
 int vp_dice_loss_bwd_f32(const float* probs, const float* targets, const float* sums, const float* gptr, float* dprobs, int B, int n,
                          float smooth, vp_stream stream) {
-  VP_REQUIRE(probs && targets && sums && dprobs && B > 0 && n > 0, "vp_dice_loss_bwd_f32: bad arguments");
-  hipLaunchKernelGGL((be_loss_bwd_kernel<true>), dim3(grid_for((size_t)n, 256, 256), B), dim3(256), 0, (hipStream_t)stream, probs,
-                     targets, sums, gptr, dprobs, B, n, 0.f, smooth);
-  return check_launch("vp_dice_loss_bwd_f32");
+  return be_loss_bwd<true>("vp_dice_loss_bwd_f32", probs, targets, sums, gptr, dprobs, B, n, 0.f, smooth, stream);
 }
 
 int vp_half_sqdiff_f32(const float* a, const float* b, float* out, size_t n, vp_stream stream) {
   VP_REQUIRE(a && b && out && n > 0, "vp_half_sqdiff_f32: bad arguments");
-  hipLaunchKernelGGL(half_sqdiff_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, a, b, out, n);
-  return check_launch("vp_half_sqdiff_f32");
+  return launch_flat("vp_half_sqdiff_f32", half_sqdiff_kernel, n, FLAT_CAP, (hipStream_t)stream, a, b, out, n);
 }
 
 int vp_half_sqdiff_rowsum_f32(const float* a, const float* b, float* out, int R, int n_per_row, vp_stream stream) {
@@ -872,9 +723,8 @@ int vp_half_sqdiff_bwd_f32(const float* a, const float* b, const float* g, float
                            int g_per_row, vp_stream stream) {
   VP_REQUIRE(a && b && g && (da || db) && R > 0 && n_per_row > 0, "vp_half_sqdiff_bwd_f32: bad arguments");
   const size_t total = (size_t)R * n_per_row;
-  hipLaunchKernelGGL(half_sqdiff_bwd_kernel, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, a, b, g, da, db, total,
+  return launch_flat("vp_half_sqdiff_bwd_f32", half_sqdiff_bwd_kernel, total, FLAT_CAP, (hipStream_t)stream, a, b, g, da, db, total,
                      n_per_row, g_per_row ? 1 : 0);
-  return check_launch("vp_half_sqdiff_bwd_f32");
 }
 
 int vp_gan_head_f32(const float* logit, int B, float coef, float* p_out, float* sums, float* dlogit, vp_stream stream) {
@@ -892,140 +742,55 @@ int vp_smooth_l1_cat_f32(const float* targets, const float* a, const float* b, i
 
 int vp_bce_bwd_f32(const float* p, const float* t, const float* gptr, float gscale, float* dp, size_t n, vp_stream stream) {
   VP_REQUIRE(p && t && dp && n > 0, "vp_bce_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(bce_bwd_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, p, t, gptr, gscale, dp, n);
-  return check_launch("vp_bce_bwd_f32");
+  return launch_flat("vp_bce_bwd_f32", bce_bwd_kernel, n, FLAT_CAP, (hipStream_t)stream, p, t, gptr, gscale, dp, n);
 }
 
 int vp_bce_sigmoid_bwd_f32(const float* p, const float* t, float gscale, float* dlogit, size_t n, vp_stream stream) {
   VP_REQUIRE(p && t && dlogit && n > 0, "vp_bce_sigmoid_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(bce_sigmoid_bwd_kernel, dim3(grid_for(n / 4 + 1, 256)), dim3(256), 0, (hipStream_t)stream, p, t, gscale, dlogit, n);
-  return check_launch("vp_bce_sigmoid_bwd_f32");
+  return launch_flat("vp_bce_sigmoid_bwd_f32", bce_sigmoid_bwd_kernel, n / 4 + 1, FLAT_CAP, (hipStream_t)stream, p, t, gscale, dlogit, n);
 }
 
 int vp_bce_sigmoid_bwd_pad_split_f32(const float* p, const float* t, float gscale, float* dlogit, void* dlogit_split,
                                      size_t npix, int C, int Cpad, vp_stream stream) {
   VP_REQUIRE(p && t && dlogit && dlogit_split && npix > 0 && C > 0 && Cpad >= C && Cpad % 8 == 0,
              "vp_bce_sigmoid_bwd_pad_split_f32: bad arguments");
-  hipLaunchKernelGGL(bce_sigmoid_bwd_pad_kernel, dim3(grid_for(npix * Cpad, 256)), dim3(256), 0, (hipStream_t)stream, p, t, gscale,
-                     dlogit, (u16_t*)dlogit_split, npix, C, Cpad);
-  return check_launch("vp_bce_sigmoid_bwd_pad_split_f32");
+  return launch_flat("vp_bce_sigmoid_bwd_pad_split_f32", bce_sigmoid_bwd_pad_kernel, npix * Cpad, FLAT_CAP, (hipStream_t)stream, p, t,
+                     gscale, dlogit, (u16_t*)dlogit_split, npix, C, Cpad);
 }
 
 int vp_upsample2x_bilinear_fwd_f32(const float* x, float* y, int B, int H, int W, int C, vp_stream stream) {
   VP_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0, "vp_upsample2x_bilinear_fwd_f32: bad arguments");
-  hipLaunchKernelGGL(upsample2x_fwd_kernel, dim3(grid_for((size_t)B * 4 * H * W * C, 256)), dim3(256), 0, (hipStream_t)stream, x, y, B, H, W, C);
-  return check_launch("vp_upsample2x_bilinear_fwd_f32");
+  return launch_flat("vp_upsample2x_bilinear_fwd_f32", upsample2x_fwd_kernel, (size_t)B * 4 * H * W * C, FLAT_CAP, (hipStream_t)stream, x,
+                     y, B, H, W, C);
 }
 
 int vp_upsample2x_bilinear_bwd_f32(const float* dy, float* dx, int B, int H, int W, int C, vp_stream stream) {
   VP_REQUIRE(dy && dx && B > 0 && H > 0 && W > 0 && C > 0, "vp_upsample2x_bilinear_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_for((size_t)B * H * W * C, 256)), dim3(256), 0, (hipStream_t)stream, dy, dx, B, H, W, C);
-  return check_launch("vp_upsample2x_bilinear_bwd_f32");
+  return launch_flat("vp_upsample2x_bilinear_bwd_f32", upsample2x_bwd_kernel, (size_t)B * H * W * C, FLAT_CAP, (hipStream_t)stream, dy, dx,
+                     B, H, W, C);
 }
 
 int vp_add_coords_f32(const float* x, float* out, int B, int H, int W, int C, int normalize, vp_stream stream) {
   VP_REQUIRE(x && out && B > 0 && H > 0 && W > 0 && C > 0, "vp_add_coords_f32: bad arguments");
-  hipLaunchKernelGGL(add_coords_kernel, dim3(grid_for((size_t)B * H * W * (C + 2), 256)), dim3(256), 0, (hipStream_t)stream, x, out, B, H, W, C, normalize);
-  return check_launch("vp_add_coords_f32");
+  return launch_flat("vp_add_coords_f32", add_coords_kernel, (size_t)B * H * W * (C + 2), FLAT_CAP, (hipStream_t)stream, x, out, B, H, W,
+                     C, normalize);
 }
 
 int vp_slice_channels_f32(const float* in, float* out, size_t npix, int Cin, int Cout, vp_stream stream) {
   VP_REQUIRE(in && out && npix > 0 && Cout > 0 && Cout <= Cin, "vp_slice_channels_f32: bad arguments");
-  hipLaunchKernelGGL(slice_channels_kernel, dim3(grid_for(npix * Cout, 256)), dim3(256), 0, (hipStream_t)stream, in, out, npix, Cin, Cout);
-  return check_launch("vp_slice_channels_f32");
+  return launch_flat("vp_slice_channels_f32", slice_channels_kernel, npix * Cout, FLAT_CAP, (hipStream_t)stream, in, out, npix, Cin, Cout);
 }
 
-int vp_adam_f32(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step,
-                float grad_scale, vp_stream stream) {
-  VP_REQUIRE(p && g && m && v && n > 0 && step >= 1, "vp_adam_f32: bad arguments");
-  VP_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0, "vp_adam_f32: arena must be 16-byte aligned");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  const int cap = 256 * 64;
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n / 4 + 1, 256, cap)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n,
-                     1.f - beta1, beta2, 1.f - beta2, eps, step_size, bc2_sqrt, grad_scale);
-  return check_launch("vp_adam_f32");
-}
-
-int vp_adam_outer_f32(float* p, float* m, float* v, const float* A, const float* Bm, int K, int R, int Cn, float lr, float beta1,
-                      float beta2, float eps, int step, float grad_scale, vp_stream stream) {
-  VP_REQUIRE(p && m && v && A && Bm && K > 0 && R > 0 && Cn > 0 && step >= 1, "vp_adam_outer_f32: bad arguments");
-  VP_REQUIRE(Cn % 4 == 0 && R % 4 == 0, "vp_adam_outer_f32: R and Cn must be multiples of 4");
-  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float bc2_sqrt = (float)sqrt(bc2);
-  const int ti = 8;      // rows per thread: 8 (142 us on the 1024 x 32768 layer) | 16 (150 us)
-  const int TI = ti == 8 ? 8 : 16;
-  const dim3 grid((unsigned)((Cn / 4 + 255) / 256), (unsigned)((R + TI - 1) / TI));
-  VP_REQUIRE(grid.y <= 65535, "vp_adam_outer_f32: too many rows");
-  if (TI == 8)
-    hipLaunchKernelGGL(adam_outer_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, p, m, v, A, Bm, K, R, Cn, 1.f - beta1, beta2, 1.f - beta2,
-                       eps, step_size, bc2_sqrt, grad_scale);
-  else
-    hipLaunchKernelGGL(adam_outer_kernel<16>, grid, dim3(256), 0, (hipStream_t)stream, p, m, v, A, Bm, K, R, Cn, 1.f - beta1, beta2, 1.f - beta2,
-                       eps, step_size, bc2_sqrt, grad_scale);
-  return check_launch("vp_adam_outer_f32");
-}
-
-int vp_rmsprop_f32(float* p, const float* g, float* sq, size_t n, float lr, float alpha, float eps, float grad_scale,
-                   vp_stream stream) {
-  VP_REQUIRE(p && g && sq && n > 0, "vp_rmsprop_f32: bad arguments");
-  hipLaunchKernelGGL(rmsprop_kernel, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, (hipStream_t)stream, p, g, sq, n, lr, alpha,
-                     1.f - alpha, eps, grad_scale);
-  return check_launch("vp_rmsprop_f32");
-}
-}
-
-// ---- F.cross_entropy(logits, labels) (mean over rows): train_BE_GAN.py:135,159, train_BE_font.py:109 ---------------------------
-// R rows of n logits, labels int64.  One workgroup; a thread owns whole rows (R = batch size, n = a handful of classes), the row
-// losses are summed in a fixed order: bit-reproducible.  prob[r][j] = softmax (kept for the backward pass).
-namespace vp {
-__global__ void __launch_bounds__(256) cross_entropy_fwd_kernel(const float* __restrict__ x, const long long* __restrict__ labels,
-                                                                float* __restrict__ loss, float* __restrict__ prob, int R, int n) {
-  __shared__ double part[256];
-  double acc = 0.0;
-  for (int r = threadIdx.x; r < R; r += 256) {
-    const float* xr = x + (size_t)r * n;
-    float m = xr[0];
-    for (int j = 1; j < n; ++j) m = fmaxf(m, xr[j]);
-    float ssum = 0.f;
-    for (int j = 0; j < n; ++j) ssum += __builtin_expf(xr[j] - m);
-    const float inv = 1.f / ssum;
-    for (int j = 0; j < n; ++j) prob[(size_t)r * n + j] = __builtin_expf(xr[j] - m) * inv;
-    const long long lb = labels[r];
-    const float xl = (lb >= 0 && lb < n) ? xr[lb] : 0.f;          // (an out-of-range label contributes lse only; the host checks)
-    acc += (double)((m + __builtin_logf(ssum)) - xl);
-  }
-  part[threadIdx.x] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < 256; ++i) t += part[i];
-    loss[0] = (float)(t / (double)R);
-  }
-}
-__global__ void cross_entropy_bwd_kernel(const float* __restrict__ prob, const long long* __restrict__ labels, const float* __restrict__ g,
-                                         float* __restrict__ dx, int R, int n) {
-  const float gs = g[0] / (float)R;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < (size_t)R * n; i += (size_t)gridDim.x * blockDim.x) {
-    const int r = (int)(i / n), j = (int)(i - (size_t)r * n);
-    dx[i] = gs * (prob[i] - (labels[r] == j ? 1.f : 0.f));
-  }
-}
-}  // namespace vp
-
-extern "C" {
 int vp_cross_entropy_fwd_f32(const float* logits, const long long* labels, float* loss, float* prob, int R, int n, vp_stream stream) {
   VP_REQUIRE(logits && labels && loss && prob && R > 0 && n > 0, "vp_cross_entropy_fwd_f32: bad arguments");
-  hipLaunchKernelGGL(vp::cross_entropy_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, loss, prob, R, n);
-  return vp::check_launch("vp_cross_entropy_fwd_f32");
+  hipLaunchKernelGGL(cross_entropy_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logits, labels, loss, prob, R, n);
+  return check_launch("vp_cross_entropy_fwd_f32");
 }
+
 int vp_cross_entropy_bwd_f32(const float* prob, const long long* labels, const float* gptr, float* dlogits, int R, int n, vp_stream stream) {
   VP_REQUIRE(prob && labels && gptr && dlogits && R > 0 && n > 0, "vp_cross_entropy_bwd_f32: bad arguments");
-  hipLaunchKernelGGL(vp::cross_entropy_bwd_kernel, dim3(vp::grid_for((size_t)R * n, 256)), dim3(256), 0, (hipStream_t)stream, prob, labels, gptr,
+  return launch_flat("vp_cross_entropy_bwd_f32", cross_entropy_bwd_kernel, (size_t)R * n, FLAT_CAP, (hipStream_t)stream, prob, labels, gptr,
                      dlogits, R, n);
-  return vp::check_launch("vp_cross_entropy_bwd_f32");
 }
-}
+
+}  // extern "C"

@@ -6,6 +6,7 @@
 // Projection (searching the latent space for the z whose decode explains a given, possibly masked, image) has no counterpart in
 // the reference: new functionality.  Its objective is the reference's per-pixel F.binary_cross_entropy(reduction="sum"), kept
 // per image, plus a Gaussian prior on z.
+#include "optim.h"
 #include "score.h"
 #include "split.h"
 
@@ -64,32 +65,11 @@ __global__ void __launch_bounds__(256) affine_relu_bwd_kernel1(const float* dy, 
 }
 
 // ---- one Adam step on the latents ------------------------------------------------------------------------------------------------
-// torch.optim.Adam's single-tensor update (no amsgrad, no weight decay) of one element:
-//   m.lerp_(g, 1-b1); v = v*b2 + (1-b2)*g*g; denom = sqrt(v)/sqrt(bc2) + eps; p -= (lr/bc1) * m/denom
-// with every rounding written out (contraction off), in the roundings adam_kernel (elementwise.hip: vp_adam_f32) applies to the
-// same element of a flat array of n elements below its streaming loop's threshold (16.7 M), so that with prior_weight = 0 the two
-// write the same bits.  adam_kernel's expression is left to the compiler, which fused v's products differently on its paths:
-// an element of a whole 16-byte quad (index < n & ~3) gets v = fma(b2, v, ((1-b2) g) g), one of the last n & 3 elements
-// v = b2 v + ((1-b2) g) g with both products rounded; m and p are fma(1-b1, g - m, m) and fma(-lr/bc1, m/denom, p) on every path.
-// tests/test_gpu_project_kernels.py holds the two kernels to each other.
-__device__ __forceinline__ void latent_adam_update(float& p, float g, float& m, float& v, bool in_quad, float one_minus_b1, float b2,
-                                                   float one_minus_b2, float eps, float step_size, float bc2_sqrt) {
-#pragma clang fp contract(off)
-  m = fmaf(one_minus_b1, g - m, m);
-  const float gg = (one_minus_b2 * g) * g;
-  v = in_quad ? fmaf(b2, v, gg) : v * b2 + gg;
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  p = fmaf(-step_size, m / denom, p);
-}
-
-// the two bias-corrected constants of step `step` (1-based), in double, as vp_adam_f32 computes them on the host
-struct AdamStep { float step_size, bc2_sqrt; };
-__device__ inline AdamStep adam_step_constants(float lr, float beta1, float beta2, int step) {
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  return {(float)((double)lr / bc1), (float)sqrt(bc2)};
-}
-
+// adam_update (optim.h) on element i of z, in the form of v that adam_kernel (optim.hip: vp_adam_f32) applies to element i of a
+// flat array of rows * Z elements below its streaming loop's threshold: ADAM_V_FMA_DECAY for an element of a whole 16-byte quad
+// (i < n & ~3), ADAM_V_TWO_PRODUCTS for the last n & 3.  With prior_weight = 0 the two kernels write the same bits;
+// tests/test_gpu_project_kernels.py holds them to each other.
+//
 // One wavefront per row of z [rows][Z], lanes stride the row.  Gradient g + prior_weight z (one fma).  The bias corrections are
 // computed here from the step count READ FROM DEVICE MEMORY: count[0] = steps taken so far, this launch is step count[0] + 1.
 // Nothing in this launch writes the counter -- latent_step_advance_kernel, a one-thread launch that follows it on the stream,
@@ -101,8 +81,8 @@ __global__ void __launch_bounds__(64) latent_adam_kernel(float* __restrict__ z, 
                                                          float* __restrict__ prior) {
   const size_t base = (size_t)blockIdx.x * Z;
   const size_t quads_end = ((size_t)gridDim.x * Z) & ~(size_t)3;
-  AdamStep k = {0.f, 1.f};
-  if (g) k = adam_step_constants(lr, beta1, beta2, count[0] + 1);
+  AdamStep k = {};
+  if (g) k = adam_step_constants(lr, beta1, beta2, eps, count[0] + 1);
   float sq = 0.f;
   for (int j = threadIdx.x; j < Z; j += 64) {
     const size_t i = base + j;
@@ -110,8 +90,7 @@ __global__ void __launch_bounds__(64) latent_adam_kernel(float* __restrict__ z, 
     sq += zv * zv;
     if (g) {
       float mv = m[i], vv = v[i];
-      latent_adam_update(zv, fmaf(prior_weight, zv, g[i]), mv, vv, i < quads_end, 1.f - beta1, beta2, 1.f - beta2, eps, k.step_size,
-                         k.bc2_sqrt);
+      adam_update(zv, fmaf(prior_weight, zv, g[i]), mv, vv, i < quads_end ? ADAM_V_FMA_DECAY : ADAM_V_TWO_PRODUCTS, 1.f, k);
       z[i] = zv;
       m[i] = mv;
       v[i] = vv;

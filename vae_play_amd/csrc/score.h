@@ -14,12 +14,6 @@ constexpr int SCORE_CHUNK = 4096;
 
 inline int score_chunks(int n) { return (n + SCORE_CHUNK - 1) / SCORE_CHUNK; }
 
-// the BCE term of reduce_partial_kernel<0> (elementwise.hip), the same expression and clamp
-__device__ __forceinline__ float bce_term(float p, float t) {
-  const float lp = fmaxf(logf(p), -100.f), lq = fmaxf(logf(1.f - p), -100.f);
-  return t * lp + (1.f - t) * lq;
-}
-
 // grid (rows, chunks): workgroup (r, c) sums elements [c * SCORE_CHUNK, min(n, (c + 1) * SCORE_CHUNK)) of row r into
 // dst[r * nchunk + c].  Where p and t sit at the same offset from a 16-byte boundary the chunk is read as up to 3 scalar head
 // elements, 16-byte loads, and up to 3 scalar tail elements; else element by element (still coalesced).  Lane partials in
@@ -82,10 +76,8 @@ static __global__ void __launch_bounds__(256) bce_rows_kernel(const float* __res
     }
   }
   for (int i = head + 4 * n4 + threadIdx.x; i < len; i += 256) one(i);
-  acc = wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) dst[(size_t)r * nchunk + c] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  acc = block_sum4(acc, sh);
+  if (threadIdx.x == 0) dst[(size_t)r * nchunk + c] = acc;
 }
 
 // one wavefront per row: the chunk partials in fp64, lanes stride the chunks, fixed-order tree

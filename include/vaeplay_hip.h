@@ -187,6 +187,12 @@ int vp_conv5_smallin_dgrad_f32(const float* small, const float* w_ref, float* bi
  * fp32 NHWC operands, reference weight layout, act none | relu; the same rows-in-K kernel as vp_conv5_smallin_dgrad_bf16x3. */
 int vp_conv5_smallin_fwd_bf16x3(const float* small, const float* w_ref, const float* bias, float* big_out, int B, int H, int W, int Csmall,
                                 int Cbig, int act, vp_stream stream);
+/* The same layer with the result written as split bf16 planes instead of fp32: out_hi = the hi plane of this launch's first image, the
+ * lo plane lies plane_elems elements behind it (plane_elems >= B * H * W * Cbig: several launches may fill consecutive pieces of one
+ * split tensor).  The planes equal, bit for bit, vp_split_f32 of what vp_conv5_smallin_fwd_bf16x3 writes; the fp32 tensor -- the
+ * discriminator's largest -- is neither written nor read back. */
+int vp_conv5_smallin_fwd_planes_bf16x3(const float* small, const float* w_ref, const float* bias, void* out_hi, size_t plane_elems, int B,
+                                       int H, int W, int Csmall, int Cbig, int act, vp_stream stream);
 size_t vp_conv5_wgrad_bf16x3_workspace_bytes(int B, int Hs, int Ws, int Cbig, int Csmall, int stride);
 int vp_conv5_wgrad_bf16x3(const void* big_split, const void* small_split, float* dw_ref,
                           int B, int Hs, int Ws, int Cbig, int Csmall, int stride,
@@ -539,6 +545,24 @@ int vp_conv5_gather_affine_f16(const void* big_split, const void* w_p0_split, co
 int vp_conv5_scatter_affine_f16(const void* small_split, const void* w_p1_split, const float* scale, const float* shift, float* out_f32,
                                 void* out_split, int B, int Hs, int Ws, int Csmall, int Cbig, int stride, int act, int out_fmt,
                                 vp_stream stream);
+
+/* ---- inference: the VAE-GAN discriminator's tap and head in eval mode, the folded DirectDecoder (csrc/infer_gan.hip) ---------------
+ * vp_disc_tap_eval_f32: c [n][64][C] = the fp32 NHWC output of the convolution of conv[recon_level] at 8 x 8 (models/networks.py:
+ * 178-183), C a multiple of 32, read once.  act_flat [n][C * 64] = relu(fma(c, scale, shift)) and feat_flat [n][C * 64] = c, both in
+ * the reference's NCHW flatten order (what fc.0 reads; the mode "REC" result); with pair_rows = P > 0 (2 P <= n)
+ * dist[i] = 1/2 sum (c[i] - c[i + P])^2 for i < P ("mse", :273).  act_flat, feat_flat and (with P = 0) dist may each be NULL.  The sum
+ * of a pair has one fixed order that depends on neither n nor the grid: no atomics, bit-reproducible, the same in any batch.
+ * vp_disc_head_eval_f32: h [n][H] = fc.0's output; per row logit = sum relu(fma(h, scale, shift)) w + bias[0] (fc.1 in eval mode,
+ * fc.3; bias is a device pointer), p = sigmoid(logit) (:198), nl_real = -log(p + 1e-3), nl_fake = -log(1 - p + 1e-3) (:274-276; 1 - p
+ * as sigmoid(-logit), without the cancellation).  Each output [n] may be NULL.  Fixed summation order per row.
+ * vp_lin_fold_f32: two bias-ed Linear layers without an activation between them as one: w_new [M][K] = w_out [M][N] w [N][K],
+ * b_new [M] = w_out b + b_out, M <= 8, fp32 fma over n = 0 .. N - 1 in that order (DirectDecoder, models/networks.py:118-148). */
+int vp_disc_tap_eval_f32(const float* c, const float* scale, const float* shift, int n, int C, float* act_flat, float* feat_flat,
+                         int pair_rows, float* dist, vp_stream stream);
+int vp_disc_head_eval_f32(const float* h, const float* scale, const float* shift, const float* w, const float* bias, int n, int H,
+                          float* logit, float* p, float* nl_real, float* nl_fake, vp_stream stream);
+int vp_lin_fold_f32(const float* w_out, const float* b_out, const float* w, const float* b, int M, int N, int K, float* w_new,
+                    float* b_new, vp_stream stream);
 
 /* ---- SCSEBlock (models/blocks.py:52-65), fp32 NHWC, forward and backward ------------------------------------------------------
  * y[b,p,ch] = x (c[b,ch] + s[b,p]) with the channel gate c = sigmoid(W2 relu(W1 mean_p(x) + b1) + b2) (W1 [C/r][C], W2 [C][C/r], the

@@ -30,7 +30,14 @@ windows: projections/s, microseconds per iteration, and whether the fused iterat
 (key ``project``).  Per launch of one iteration it also lists the time between device events around it (``launches``: where the
 iteration's time goes).
 
+``--vaegan`` adds the VAE-GAN leg (key ``vaegan``), at 128x128x1 batch 32 and 64x64x1 batch 128: ``FusedVAEGANInference.forward`` and
+``.similarity``, eager and replayed, against the drop-in ``VaeGan`` in ``.eval()`` under ``set_conv_precision("bf16x3")`` computing the
+same outputs (``net(x, eps=eps)``, ``discriminator.forward_rec_and_gan`` on (x, x_tilde), the loss terms with torch), in the same
+alternating windows; and, with device events around each launch, the planes-writing stem against stem + split and the tap kernel
+against the launches it replaces, at 2B rows.
+
     python tools/bench_infer.py --out bench_out/infer.json
+    python tools/bench_infer.py --vaegan --vaegan-only --out bench_out/infer_vaegan.json
     python tools/bench_infer.py --project 20 --project-only --iters 5 --out bench_out/infer_project.json
     python tools/bench_infer.py --precisions f16,bf16x3,f32 --layers --score 8 --out bench_out/infer_f16.json
     python tools/bench_infer.py --score 8 --score-only --out bench_out/infer_score.json
@@ -447,6 +454,138 @@ def bench_layers_f16(C, S, z, B, args):
     return res
 
 
+VAEGAN_SHAPES = {"vaegan_128x128x1_z128_b32": (128, 128, 32), "vaegan_64x64x1_z64_b128": (64, 64, 128)}      # (S, z, B)
+
+
+def _launch_ab(variants, args):
+    """{name: [launch, ...]} with device events around EACH launch, the variants alternating: per variant the summed medians of its
+    launches in microseconds, min and max of the per-repetition sums"""
+    def once(fns):
+        ev = []
+        for fn in fns:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            ev.append((e0, e1))
+        torch.cuda.synchronize()
+        return [e0.elapsed_time(e1) * 1e3 for e0, e1 in ev]
+    for fns in variants.values():
+        for _ in range(args.warmup):
+            once(fns)
+    t = {k: [] for k in variants}
+    for _ in range(args.reps * args.iters):
+        for k, fns in variants.items():
+            t[k].append(once(fns))
+    out = {}
+    for k, runs in t.items():
+        sums = [sum(r) for r in runs]
+        out[k] = {"us": statistics.median(sums), "min": min(sums), "max": max(sums),
+                  "per_launch_us": [statistics.median(r[i] for r in runs) for i in range(len(runs[0]))]}
+    return out
+
+
+def bench_vaegan_kernels(S, B, Cd):
+    """the launches for the A/B of the two fused kernels at 2B rows: the planes-writing stem against stem + split, the tap kernel
+    against normalise pass + two transposes + row sum"""
+    from vae_play_amd import _lib, ops
+    from ctypes import c_void_p
+    lib = _lib.load()
+    P = lambda t: None if t is None else c_void_p(t.data_ptr())      # noqa: E731
+    s = c_void_p(torch.cuda.current_stream().cuda_stream)
+    n2, C0 = 2 * B, 32
+    x = torch.rand((n2, 1, S, S), device="cuda")
+    w, bias = torch.randn((C0, 1, 5, 5), device="cuda") * 0.1, torch.randn(C0, device="cuda") * 0.1
+    n0 = n2 * S * S * C0
+    y0, y0s = torch.empty(n0, device="cuda"), torch.empty((2, n0), dtype=torch.int16, device="cuda")
+    half = n0 // 2
+    stem = {
+        "planes_two_halves": [lambda k=k: _lib.check(lib.vp_conv5_smallin_fwd_planes_bf16x3(
+            c_void_p(x.data_ptr() + 4 * k * B * S * S), P(w), P(bias), c_void_p(y0s.data_ptr() + 2 * k * half), n0, B, S, S, 1, C0,
+            ops.ACT_RELU, s)) for k in range(2)],
+        "fp32_then_split": [lambda: _lib.check(lib.vp_conv5_smallin_fwd_bf16x3(P(x), P(w), P(bias), P(y0), n2, S, S, 1, C0, ops.ACT_RELU, s)),
+                            lambda: _lib.check(lib.vp_split_f32(P(y0), P(y0s), n0, s))],
+    }
+    c = torch.randn((n2, 64, Cd), device="cuda")
+    a, act, feat = torch.empty_like(c), torch.empty((n2, Cd * 64), device="cuda"), torch.empty((n2, Cd * 64), device="cuda")
+    sc, sh = torch.rand(Cd, device="cuda") + 0.5, torch.randn(Cd, device="cuda")
+    zeros, ones, dist = torch.zeros(Cd, device="cuda"), torch.ones(Cd, device="cuda"), torch.empty(B, device="cuda")
+    tap = {
+        "tap_kernel": [lambda: _lib.check(lib.vp_disc_tap_eval_f32(P(c), P(sc), P(sh), n2, Cd, P(act), None, B, P(dist), s))],
+        "pass_transpose_rowsum": [
+            lambda: _lib.check(lib.vp_bn_act_fwd_f32(P(c), P(zeros), P(ones), P(sc), P(sh), P(a), n2 * 64, Cd, ops.ACT_RELU, 0.0, s)),
+            lambda: _lib.check(lib.vp_nhwc_to_nchw_f32(P(a), P(act), n2, Cd, 8, 8, s)),
+            lambda: _lib.check(lib.vp_half_sqdiff_rowsum_f32(P(c), c_void_p(c.data_ptr() + 4 * B * 64 * Cd), P(dist), B, 64 * Cd, s))],
+    }
+    return stem, tap
+
+
+def bench_vaegan(name, S, z, B, args):
+    """``--vaegan``: FusedVAEGANInference.forward and .similarity (eager, and replayed as a hipGraph) against the drop-in VaeGan in
+    ``.eval()`` under set_conv_precision("bf16x3") computing the same outputs -- net(x, eps=eps), forward_rec_and_gan on
+    (x, x_tilde), the loss terms with torch -- in alternating windows; then the two fused kernels against the launches they replace"""
+    import vae_play_amd as V
+    torch.manual_seed(0)
+    net = V.VaeGan(S, z).cuda().eval()
+    randomise_bn(net, 1)
+    g = torch.Generator().manual_seed(2)
+    x = torch.rand((B, 1, S, S), generator=g).cuda()
+    eps = torch.randn((B, z), generator=g).cuda()
+    eager, graph = V.FusedVAEGANInference(net, B), V.FusedVAEGANInference(net, B)
+    graph.enable_gan()
+    graph.capture()
+    none = x[:0]
+
+    def modules_forward():
+        return net(x, eps=eps)
+
+    def modules_similarity():
+        xt, params = net(x, eps=eps)
+        feat, p = net.discriminator.forward_rec_and_gan(x, xt, none)
+        p = p.reshape(-1)
+        return {"x_tilde": xt, "params": params, "nle": (0.5 * (x - xt) ** 2).flatten(1).sum(1),
+                "mse": (0.5 * (feat[:B] - feat[B:]) ** 2).sum(1), "p_x": p[:B], "p_x_tilde": p[B:],
+                "bce_dis_original": -torch.log(p[:B] + 1e-3), "bce_dis_predicted": -torch.log(1 - p[B:] + 1e-3)}
+    out = {}
+    V.set_conv_precision("bf16x3")
+    try:
+        with torch.no_grad():
+            ref, got = modules_similarity(), eager.similarity(x, eps)
+            # the paths compute the same thing (recorded, not asserted: the parity tests assert)
+            out["max_rel_diff_fused_vs_modules"] = {k: ((got[k] - ref[k]).abs().max() / ref[k].abs().max()).item() for k in ref}
+            legs = {"forward": {"modules": modules_forward, "fused": lambda: eager.forward(x, eps), "fused_graph": lambda: graph.forward(x, eps)},
+                    "similarity": {"modules": modules_similarity, "fused": lambda: eager.similarity(x, eps),
+                                   "fused_graph": lambda: graph.similarity(x, eps)}}
+            for leg, variants in legs.items():
+                r = _with_spread(ab(variants, args.iters, args.reps, args.warmup), B, "images_per_s")
+                res = dict(r)
+                for k in ("fused", "fused_graph"):
+                    saved, spread = r["modules"]["ms"] - r[k]["ms"], r["modules"]["spread_ms"] + r[k]["spread_ms"]
+                    res[k + "_vs_modules"] = {"speedup": r["modules"]["ms"] / r[k]["ms"], "saved_ms": saved, "sum_of_spreads_ms": spread,
+                                              "faster_by_more_than_spreads": bool(saved > spread)}
+                out[leg] = res
+                print(f"{name} {leg}: modules {r['modules']['ms']:.3f} ms [{r['modules']['min']:.3f}, {r['modules']['max']:.3f}]  "
+                      f"fused {r['fused']['ms']:.3f} [{r['fused']['min']:.3f}, {r['fused']['max']:.3f}]  "
+                      f"graph {r['fused_graph']['ms']:.3f} [{r['fused_graph']['min']:.3f}, {r['fused_graph']['max']:.3f}]  "
+                      f"fused x{res['fused_vs_modules']['speedup']:.2f} graph x{res['fused_graph_vs_modules']['speedup']:.2f}", flush=True)
+            # graph against eager AFTER the timing loops, as the scoring leg does (DESIGN.md section 14.1)
+            after_e, after_g = eager.similarity(x, eps), graph.similarity(x, eps)
+            out["graph_equals_eager"] = all(bool(torch.equal(after_g[k], after_e[k])) for k in after_e)
+            out["eager_equals_its_first_call"] = all(bool(torch.equal(after_e[k], got[k])) for k in got)
+            stem, tap = bench_vaegan_kernels(S, B, eager._gan.disc.Cd)
+            for what, variants in (("stem", stem), ("tap", tap)):
+                r = _launch_ab(variants, args)
+                (new, rn), (old, ro) = r.items()
+                r["saved_us"], r["sum_of_spreads_us"] = ro["us"] - rn["us"], (rn["max"] - rn["min"]) + (ro["max"] - ro["min"])
+                r["faster_by_more_than_spreads"] = bool(r["saved_us"] > r["sum_of_spreads_us"])
+                out["kernel_" + what] = r
+                print(f"{name} kernel {what}: {new} {rn['us']:.1f} us [{rn['min']:.1f}, {rn['max']:.1f}]  {old} {ro['us']:.1f} us "
+                      f"[{ro['min']:.1f}, {ro['max']:.1f}]  per launch {rn['per_launch_us']} vs {ro['per_launch_us']}", flush=True)
+    finally:
+        V.set_conv_precision("f32")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=40, help="calls per timed window")
@@ -459,6 +598,10 @@ def main():
     ap.add_argument("--project", type=int, default=0, metavar="STEPS",
                     help="add the projection leg: project() with STEPS iterations against the modules under autograd + torch.optim.Adam")
     ap.add_argument("--project-only", action="store_true", help="with --project: skip every other leg")
+    ap.add_argument("--vaegan", action="store_true",
+                    help="add the VAE-GAN leg (128x128x1 batch 32, 64x64x1 batch 128): FusedVAEGANInference forward / similarity "
+                         "against the drop-in VaeGan in eval mode, and the two fused kernels against the launches they replace")
+    ap.add_argument("--vaegan-only", action="store_true", help="with --vaegan: skip every other leg")
     ap.add_argument("--shapes", default=",".join(SHAPES), help="comma-separated subset of: " + ", ".join(SHAPES))
     ap.add_argument("--precisions", default="bf16x3,f32", help="comma-separated subset of: f16, bf16x3, f32")
     ap.add_argument("--out", default="bench_out/infer.json")
@@ -476,6 +619,14 @@ def main():
     module_precs = [p for p in precs if p != "f16"]      # (the module path has no one-product mode to compare against)
     if args.project < 0 or (args.project_only and not args.project):
         raise SystemExit("--project takes a positive STEPS; --project-only needs it")
+    if args.vaegan_only and not args.vaegan:
+        raise SystemExit("--vaegan-only needs --vaegan")
+    if args.vaegan:
+        doc["vaegan"] = {name: bench_vaegan(name, *shape, args) for name, shape in VAEGAN_SHAPES.items()}
+    if args.vaegan_only:
+        args.project = args.score = 0
+        precs = module_precs = []
+        args.score_only = True          # (no reconstruct / decode / encode legs)
     if args.project:
         doc["project"] = {}
         for name in args.shapes.split(","):

@@ -9,8 +9,9 @@ from .networks import (VAE, Decoder, DecoderBlock, DirectDecoder, Discriminator,
 from .functional import (binary_cross_entropy, get_conv_precision, kl_divergence, set_conv_precision,  # noqa: F401
                          vae_loss)
 from .infer import FusedVAEInference  # noqa: F401
+from .infer_gan import FusedVAEGANInference  # noqa: F401
 
 __all__ = ["VAE", "VaeGan", "Encoder", "Decoder", "Discriminator", "DirectDecoder", "EncoderBlock", "DecoderBlock",
            "reparameterize", "init_parameters",
            "binary_cross_entropy", "kl_divergence", "vae_loss", "set_conv_precision", "get_conv_precision",
-           "FusedVAEInference"]
+           "FusedVAEInference", "FusedVAEGANInference"]

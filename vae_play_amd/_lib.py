@@ -169,6 +169,10 @@ SIGNATURES = {
     "vp_conv5_scatter_affine_f32": (c_int, [P] * 6 + [c_int] * 7 + [P]),
     "vp_conv5_gather_affine_f16": (c_int, [P] * 6 + [c_int] * 8 + [P]),
     "vp_conv5_scatter_affine_f16": (c_int, [P] * 6 + [c_int] * 8 + [P]),
+    "vp_conv5_smallin_fwd_planes_bf16x3": (c_int, [P, P, P, P, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    "vp_disc_tap_eval_f32": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P, P]),
+    "vp_disc_head_eval_f32": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
+    "vp_lin_fold_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P]),
     "vp_scse_workspace_bytes": (c_size_t, [c_int] * 4),
     "vp_scse_fwd_f32": (c_int, [P] * 12 + [c_int] * 5 + [P, c_size_t, P]),
     "vp_scse_bwd_f32": (c_int, [P] * 16 + [c_int] * 5 + [P, c_size_t, P]),

@@ -105,6 +105,13 @@ __device__ __forceinline__ void sigmoid_pair(float x, float e, float& p, float& 
   q = x >= 0.f ? small : big;
 }
 
+// -log(p + 1e-3) of a probability p with q = 1 - p from sigmoid_pair (VaeGan.loss, models/networks.py:274-276), every value relative
+// to itself: towards p = 1 the sum p + 1e-3 rounds at 6e-8 next to a result of -1e-3 -- 5e-5 of it -- so that side is formed as
+// -log1p(1e-3 - q).  The other side is the expression of the training step's GAN head (gan_head_kernel, whose bits stay as they are).
+__device__ __forceinline__ float neg_log_floor(float p, float q) {
+  return p <= 0.5f ? -logf(p + 1e-3f) : -log1pf(1e-3f - q);
+}
+
 // ---- host launch sequences stated once ---------------------------------------------------------------------------------------------
 // a flat kernel of 256-thread workgroups over `items` work items, its grid capped at `cap` workgroups (grid_for)
 constexpr unsigned FLAT_CAP = 256 * 8;

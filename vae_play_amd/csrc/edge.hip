@@ -349,10 +349,14 @@ int tapm_wgrad_f32_launch(const float* big_f32, const float* small_f32, float* d
 // FWD = false: the input gradient above (taps flipped, weights [NIN][CF][5][5]);  FWD = true: the FORWARD pass of a stride-1 conv with
 // 1 | 3 input channels, big_out[b,h,w,cf] = act(bias[cf] + sum_{r,q,n} small[b, h+r-2, w+q-2, n] * W[cf][n][r][q]) (weights
 // [CF][NIN][5][5], act none | relu): the VAE-GAN discriminator's first layer, models/networks.py:160-163.  CF = 64 | 32 wide channels.
-template <int NIN, int CF, bool FWD>
+// PLANES (forward only): the epilogue writes the result as split bf16 planes -- ``out`` is the hi plane of the launch's first image,
+// the lo plane lies ``plane`` elements behind it -- the planes vp_split_f32 makes of the fp32 value, which is then never stored.
+template <int NIN, int CF, bool FWD, bool PLANES = false>
 __global__ void __launch_bounds__(512, 2) dgrad_rowk_kernel(const float* __restrict__ dlogit, const float* __restrict__ w,
                                                             float* __restrict__ out, int H, int W, int tiles_x, int tiles_per_img,
-                                                            int ntiles, const float* __restrict__ bias = nullptr, int act = ACT_NONE) {
+                                                            int ntiles, const float* __restrict__ bias = nullptr, int act = ACT_NONE,
+                                                            size_t plane = 0) {
+  static_assert(FWD || !PLANES, "planes are written by the forward form");
   static_assert(CF == 64 || CF == 32, "wide channel count");
   constexpr int NJT = CF / 32;
   constexpr int TR = 8, TC = 32, PR = TR + 4, PC = (TC + 4) * NIN + 8;     // patch: 12 rows x (36 pixels x NIN floats, + slack)
@@ -452,7 +456,18 @@ __global__ void __launch_bounds__(512, 2) dgrad_rowk_kernel(const float* __restr
           const int ww = w0 + (e & 3) + 8 * (e >> 2) + 4 * lh;
           float v = acc[jt][e] + bv;
           if (FWD && act == ACT_RELU) v = v > 0.f ? v : 0.f;
-          if (ww < W) out[((size_t)(b * H + h) * W + ww) * CF + 32 * jt + li] = v;
+          const size_t o = ((size_t)(b * H + h) * W + ww) * CF + 32 * jt + li;
+          if constexpr (PLANES) {
+            if (ww < W) {
+              u16_t hh, ll;
+              split_f32(v, hh, ll);
+              u16_t* const hi = reinterpret_cast<u16_t*>(out);
+              hi[o] = hh;
+              hi[plane + o] = ll;
+            }
+          } else {
+            if (ww < W) out[o] = v;
+          }
         }
       }
     }
@@ -601,10 +616,10 @@ int vp_conv5_smallin_dgrad_bf16x3(const float* small, const float* w_ref, float*
   const int grid = ntiles < 512 ? ntiles : 512;                 // persistent: two workgroups (8 waves each) per CU
   if (Csmall == 3)
     hipLaunchKernelGGL((dgrad_rowk_kernel<3, 64, false>), dim3(grid), dim3(512), 0, (hipStream_t)stream, small, w_ref, big_out, H, W, tiles_x,
-                       tiles_x * tiles_y, ntiles, (const float*)nullptr, 0);
+                       tiles_x * tiles_y, ntiles, (const float*)nullptr, 0, (size_t)0);
   else
     hipLaunchKernelGGL((dgrad_rowk_kernel<1, 64, false>), dim3(grid), dim3(512), 0, (hipStream_t)stream, small, w_ref, big_out, H, W, tiles_x,
-                       tiles_x * tiles_y, ntiles, (const float*)nullptr, 0);
+                       tiles_x * tiles_y, ntiles, (const float*)nullptr, 0, (size_t)0);
   return check_launch("vp_conv5_smallin_dgrad_bf16x3");
 }
 
@@ -631,11 +646,27 @@ int vp_conv5_smallin_fwd_bf16x3(const float* small, const float* w_ref, const fl
   const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8, ntiles = B * tiles_x * tiles_y;
   const int grid = ntiles < 512 ? ntiles : 512;
 #define VP_ROWK_FWD(NI, CFF) hipLaunchKernelGGL((dgrad_rowk_kernel<NI, CFF, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, small, w_ref, big_out, \
-                                                H, W, tiles_x, tiles_x * tiles_y, ntiles, bias, act)
+                                                H, W, tiles_x, tiles_x * tiles_y, ntiles, bias, act, (size_t)0)
   if (Cbig == 64) { if (Csmall == 3) VP_ROWK_FWD(3, 64); else VP_ROWK_FWD(1, 64); }
   else { if (Csmall == 3) VP_ROWK_FWD(3, 32); else VP_ROWK_FWD(1, 32); }
 #undef VP_ROWK_FWD
   return check_launch("vp_conv5_smallin_fwd_bf16x3");
+}
+
+int vp_conv5_smallin_fwd_planes_bf16x3(const float* small, const float* w_ref, const float* bias, void* out_hi, size_t plane_elems, int B,
+                                       int H, int W, int Csmall, int Cbig, int act, vp_stream stream) {
+  VP_REQUIRE(small && w_ref && out_hi && B > 0 && H > 0 && W > 0, "vp_conv5_smallin_fwd_planes_bf16x3: bad arguments");
+  VP_REQUIRE((Cbig == 32 || Cbig == 64) && (Csmall == 1 || Csmall == 3), "vp_conv5_smallin_fwd_planes_bf16x3: needs 1 or 3 input and 32 or 64 output channels");
+  VP_REQUIRE(act == VP_ACT_NONE || act == VP_ACT_RELU, "vp_conv5_smallin_fwd_planes_bf16x3: activation none|relu");
+  VP_REQUIRE(plane_elems >= (size_t)B * H * W * Cbig, "vp_conv5_smallin_fwd_planes_bf16x3: the lo plane would overlap the hi plane");
+  const int tiles_x = (W + 31) / 32, tiles_y = (H + 7) / 8, ntiles = B * tiles_x * tiles_y;
+  const int grid = ntiles < 512 ? ntiles : 512;
+#define VP_ROWK_PLANES(NI, CFF) hipLaunchKernelGGL((dgrad_rowk_kernel<NI, CFF, true, true>), dim3(grid), dim3(512), 0, (hipStream_t)stream, small, w_ref, \
+                                                   (float*)out_hi, H, W, tiles_x, tiles_x * tiles_y, ntiles, bias, act, plane_elems)
+  if (Cbig == 64) { if (Csmall == 3) VP_ROWK_PLANES(3, 64); else VP_ROWK_PLANES(1, 64); }
+  else { if (Csmall == 3) VP_ROWK_PLANES(3, 32); else VP_ROWK_PLANES(1, 32); }
+#undef VP_ROWK_PLANES
+  return check_launch("vp_conv5_smallin_fwd_planes_bf16x3");
 }
 
 }

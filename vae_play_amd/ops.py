@@ -842,6 +842,19 @@ def conv5_smallin_fwd_bf16x3(x, weight, bias, act: int = ACT_NONE):
     return y
 
 
+def conv5_smallin_fwd_planes_bf16x3(x, weight, bias, act: int = ACT_NONE, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the same layer with the result written as split bf16 planes (2, B * H * W * Cout) int16 -- vp_split_f32 of the fp32 result, bit
+    for bit -- into ``out`` when given"""
+    B, Cin, H, W = x.shape
+    Cout = weight.shape[0]
+    assert _is_nhwc(x) and weight.is_contiguous()
+    n = B * H * W * Cout
+    out = empty_split(n, x) if out is None else out
+    assert out.shape == (2, n) and out.dtype == torch.int16 and out.is_contiguous()
+    _lib.call("vp_conv5_smallin_fwd_planes_bf16x3", _p(x), _p(weight), _p(bias), _pv(out), n, B, H, W, Cin, Cout, act, _stream())
+    return out
+
+
 def conv5_smallout_bf16x3(x, w_p0, bias, act: int = ACT_NONE):
     """act(bias + conv5x5 stride 1) down to 1 | 3 channels; x fp32 NHWC, w_p0 [Cout][25][Cin] fp32."""
     B, Cin, H, W = x.shape
@@ -946,6 +959,32 @@ def bn_fold(gamma, beta, running_mean, running_var, eps: float):
     scale, shift, rstd = (torch.empty(C, dtype=torch.float32, device=running_mean.device) for _ in range(3))
     _lib.call("vp_bn_fold_f32", _p(gamma), _p(beta), _p(running_mean), _p(running_var), float(eps), _p(scale), _p(shift), _p(rstd), C, _stream())
     return scale, shift, rstd
+
+
+# ---- inference: the VAE-GAN discriminator's tap and head, the fold of two Linear layers (csrc/infer_gan.hip) ---------------------
+def disc_tap_eval(c, scale, shift, act_flat=None, feat_flat=None, pair_rows: int = 0, dist=None) -> None:
+    """c (n, 64, C) fp32 NHWC at 8x8 -> act_flat = relu(fma(c, scale, shift)) and feat_flat = c, (n, C * 64) in NCHW-flat order;
+    dist[i] = 1/2 sum (c[i] - c[i + pair_rows])^2.  Outputs are written into the tensors given (None: not wanted)."""
+    n, hw, C = c.shape
+    assert hw == 64 and c.is_contiguous()
+    _lib.call("vp_disc_tap_eval_f32", _p(c), _p(scale), _p(shift), n, C, _p(act_flat), _p(feat_flat), int(pair_rows), _p(dist), _stream())
+
+
+def disc_head_eval(h, scale, shift, w, bias, logit=None, p=None, nl_real=None, nl_fake=None) -> None:
+    """h (n, H): logit = sum relu(fma(h, scale, shift)) w + bias, p = sigmoid(logit), nl_real = -log(p + 1e-3),
+    nl_fake = -log(1 - p + 1e-3), each (n,), written into the tensors given (None: not wanted)"""
+    n, H = h.shape
+    assert h.is_contiguous()
+    _lib.call("vp_disc_head_eval_f32", _p(h), _p(scale), _p(shift), _p(w), _p(bias), n, H, _p(logit), _p(p), _p(nl_real), _p(nl_fake),
+              _stream())
+
+
+def lin_fold(w_out, b_out, w, b, w_new, b_new) -> None:
+    """w_new (M, K) = w_out (M, N) w (N, K), b_new (M) = w_out b + b_out: two Linear layers without an activation between them as one"""
+    M, N = w_out.shape
+    K = w.shape[1]
+    assert w.shape[0] == N and w_out.is_contiguous() and w.is_contiguous()
+    _lib.call("vp_lin_fold_f32", _p(w_out), _p(b_out), _p(w), _p(b), M, N, K, _p(w_new), _p(b_new), _stream())
 
 
 AFFINE_PRECISION = {"bf16x3": 0, "f32": 1, "f16": 2}      # precision codes of vp_conv5_affine_supported

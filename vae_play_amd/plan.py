@@ -435,6 +435,12 @@ class PlanBuilder:
                      side=k, side_args={3 + len(geom): self.wgrad_cus}, **kw)
 
     # ---- the end of a plan ----
+    def dense_workspace(self, prefix: str = ""):
+        """the dense layers' workspace alone: the end of a builder that queued no weight pack (``finish`` needs at least one)"""
+        wsg = self.ws(f"{prefix}gemm.ws", self._gemm_need)
+        for a in self._gemm_calls:
+            a[13], a[14] = _ptr(wsg), wsg.numel() * 4
+
     def finish(self, fwd: _Plan, prefix: str = ""):
         """batched weight re-pack at the head of the forward plan, the dense layers' workspace; sets the step's
         ``_n_side_events``.  ``prefix``: of a builder that extends a finished plan (its workspace's name, its array of pack jobs)"""

@@ -1,6 +1,7 @@
 """The sections the fused plans are made of, each stated once on top of ``plan.PlanBuilder``: the im2col stem, the stride-2 gather
 block (Conv2d + BatchNorm + ReLU), the stride-2 scatter block (ConvTranspose2d + BatchNorm + ReLU), the encoder head, the decoder
-trunk and the final sigmoid convolution.  engine.FusedVAEStep, engine_gan.FusedVAEGANStep and infer.FusedVAEInference compose them;
+trunk, the final sigmoid convolution and the VAE-GAN discriminator in eval mode.  engine.FusedVAEStep, engine_gan.FusedVAEGANStep,
+infer.FusedVAEInference and infer_gan.FusedVAEGANInference compose them;
 a kernel-routing decision of a section is taken here and nowhere else.
 
 A section object is ONE pass of one layer (or group of layers): its constructor allocates the pass's buffers and queues its weight
@@ -12,6 +13,7 @@ the tensor in ``step._bufs`` -- and never point a launch at a tensor of their ow
 every pointer of every plan after a garbage collection)."""
 from __future__ import annotations
 
+from ctypes import c_void_p
 from types import SimpleNamespace
 
 from . import ops
@@ -313,6 +315,72 @@ class EncoderHead:
         b.lin_dgrad(plan, self.dh, self.fc_lin.weight, out, Bn, H1, self.F0)
         plan.hook("enc_dense_done")
         plan.add("vp_nchw_to_nhwc_f32", P(out), P(out_nhwc), Bn, self.size, 8, 8)
+
+
+# ---- the VAE-GAN discriminator in eval mode ----------------------------------------------------------------------------------
+class DiscriminatorEval:
+    """Discriminator (models/networks.py:151-198) in eval mode over 2 * ``Bn`` one-channel images, two halves of ``Bn`` that may come
+    from different buffers (the images; their reconstructions): one pass gives the mode "GAN" score and the mode "REC" features.
+
+      stem    conv[0], 5x5 stride 1 + bias + ReLU, one launch per half, each writing its half of the split planes directly;
+      body    the gather blocks before the tap in eval form, then the tap block's convolution -- the LAST block (recon_level ==
+              iter_level) -- as the plain launch into fp32 ``c``: its pre-BatchNorm output is a result, so it takes no affine epilogue;
+      tap     one launch: eval BatchNorm + ReLU of ``c`` in the flatten's order (what fc.0 reads), the features, the feature distance;
+      head    fc.0, then one launch for fc.1 (eval BatchNorm + ReLU), fc.3, the sigmoid and the two log terms.
+
+    The constructor allocates the buffers, queues the weight packs, emits the folds into ``prep`` and builds ``body`` and ``head``,
+    which every list shares; ``stem`` and ``tap`` are emitted per list (their sources and outputs differ)."""
+
+    def __init__(self, b: PlanBuilder, disc, Bn: int, S: int, prep: _Plan, tag: str = "gan.disc"):
+        convs = list(disc.conv)
+        if disc.recon_levl != len(convs) - 1:
+            raise NotImplementedError("the fused plan taps the discriminator's last block (VaeGan's own construction)")
+        self.b, self.tag, self.Bn, self.S, self.n2 = b, tag, Bn, S, 2 * Bn
+        self.conv0 = convs[0][0]
+        self.C0 = self.conv0.weight.shape[0]
+        if self.C0 not in (32, 64) or self.conv0.weight.shape[1] != 1:
+            raise NotImplementedError("discriminator stem must be 1 -> 32 | 64 channels")
+        n2 = self.n2
+        self.half0 = Bn * S * S * self.C0                                   # elements of one half of the stem's output
+        self.y0s = b.sbuf(f"{tag}0.ys", 2 * self.half0)
+        blocks = gather_stack(b, tag, convs[1:], n2, S, None, self.y0s, train=False, first_index=1)
+        if not all(k.is16 for k in blocks):
+            raise NotImplementedError("discriminator widths must be multiples of 8")
+        self.blocks, self.last = blocks, blocks[-1]
+        last = self.last
+        self.Cd, self.nf = last.Cout, 64 * last.Cout
+        if self.Cd % 32:
+            raise NotImplementedError("the tap kernel takes channel counts that are multiples of 32")
+        self.body = _Plan()
+        for blk in blocks[:-1]:
+            blk.fwd_eval(self.body, prep)
+        self.c = b.buf(f"{last.tag}.c", last.R * last.Cout)                 # the tap: pre-BatchNorm output of the last block, NHWC
+        b.conv5(self.body, 0, last.arith, last.src, last.p0, self.c, last.geom, flops=last.fl, tag=f"{last.tag}.fwd")
+        self.tap_scale, self.tap_shift, _ = b.bn_fold(prep, last.tag, last.bn)
+        self.act = last.a                                                   # relu(bn(c)) in the flatten's order
+        fc0, fc_bn, fc3 = disc.fc[0], disc.fc[1], disc.fc[3]
+        self.Hd = fc0.weight.shape[0]
+        self.h = b.buf(f"{tag}.h", n2 * self.Hd)
+        self.logit, self.p = b.buf(f"{tag}.logit", n2), b.buf(f"{tag}.p", n2)
+        self.nl_real, self.nl_fake = b.buf(f"{tag}.nl_real", n2), b.buf(f"{tag}.nl_fake", n2)
+        scale, shift, _ = b.bn_fold(prep, f"{tag}.fc", fc_bn)
+        self.head = _Plan()
+        b.lin_fwd(self.head, self.act, fc0.weight, None, self.h, n2, self.Hd, self.nf)
+        self.head.add("vp_disc_head_eval_f32", P(self.h), P(scale), P(shift), P(fc3.weight), P(fc3.bias), n2, self.Hd, P(self.logit),
+                      P(self.p), P(self.nl_real), P(self.nl_fake), tag=f"{tag}.head")
+
+    def stem(self, plan: _Plan, src_a, src_b):
+        """``src_a`` / ``src_b``: the fp32 images of the two halves, (Bn, 1, S, S) each, read where they are"""
+        Bn, S, C0 = self.Bn, self.S, self.C0
+        for half, src in enumerate((src_a, src_b)):
+            hi = c_void_p(self.y0s.data_ptr() + 2 * half * self.half0)      # (int16 planes: 2 bytes per element)
+            plan.add("vp_conv5_smallin_fwd_planes_bf16x3", P(src), P(self.conv0.weight), P(self.conv0.bias), hi, 2 * self.half0,
+                     Bn, S, S, 1, C0, ops.ACT_RELU, flops=50.0 * Bn * S * S * C0, tag=f"{self.tag}0.fwd{'ab'[half]}")
+
+    def tap(self, plan: _Plan, feat, pair_rows: int, dist):
+        """``feat``: where the features go (or None); ``pair_rows`` = Bn with ``dist``: the distance of half a to half b per image"""
+        plan.add("vp_disc_tap_eval_f32", P(self.c), P(self.tap_scale), P(self.tap_shift), self.n2, self.Cd, P(self.act), P(feat),
+                 pair_rows, P(dist), tag=f"{self.last.tag}.tap")
 
 
 # ---- final sigmoid convolution -----------------------------------------------------------------------------------------------

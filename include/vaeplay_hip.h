@@ -84,7 +84,9 @@ int vp_conv5_scatter_stats_f32(const float* small, const float* w_p1, float* big
  * ks = 4 (padding 1) is the Style-GAN generator's kernel: myConv2d(.., 4, 2) and nn.ConvTranspose2d(in, out, 4, 2, 1),
  * models/network_Style_GAN.py:49,95-98,116.
  * The big side is passed explicitly (Hb, Wb) so odd sizes work: Hs = floor((Hb + 2*pad - ks)/stride) + 1.
- * Weights: reference tensor W[Csmall][Cbig][ks][ks]; packed p0 = [Csmall][ks*ks][Cbig], p1 = [Cbig][ks*ks][Csmall]. */
+ * Weights: reference tensor W[Csmall][Cbig][ks][ks]; packed p0 = [Csmall][ks*ks][Cbig], p1 = [Cbig][ks*ks][Csmall].
+ * The gather family's epilogue: act(acc + bias[n]) with act none | sigmoid | relu (relu: a convolution whose eval-mode BatchNorm
+ * is folded into weight and bias, vp_be_fold_conv_f32). */
 int vp_pack_w_f32(const float* w_ref, float* p0, float* p1, int Csmall, int Cbig, int ks, vp_stream stream);
 int vp_conv_gather_f32(const float* big, const float* w_p0, const float* bias, float* small_out,
                        int B, int Hs, int Ws, int Hb, int Wb, int Cbig, int Csmall, int ks, int stride, int act, vp_stream stream);
@@ -563,6 +565,37 @@ int vp_disc_head_eval_f32(const float* h, const float* scale, const float* shift
                           float* logit, float* p, float* nl_real, float* nl_fake, vp_stream stream);
 int vp_lin_fold_f32(const float* w_out, const float* b_out, const float* w, const float* b, int M, int N, int K, float* w_new,
                     float* b_new, vp_stream stream);
+
+/* ---- inference: the mask / edge heads of models/networks_BE.py:39-66 in eval mode (csrc/be_infer.hip) ---------------
+ * MaskNet / EdgeNet = Up(c, c/4, coord) -> Up(c/4, c/8, coord) -> three bias-only 3x3 convolutions, as the reference runs them for
+ * inference (test_BE.py:92-98).  Exact fp32, NHWC, `heads` heads per launch: tensors are [heads][B][H][W][C], x_head_stride = floats
+ * between two heads' inputs (0: every head reads the same map, as the first Up block does), parameter blocks are packed per head.
+ * vp_be_up_infer_f32: one eval-mode Up(cin, cmid, if_add_coord=True) block (models/blocks.py:129-146) in ONE launch: the 3x3
+ * convolution cin + 2 -> cmid over x and the two unnormalised coordinate channels (column, row; computed from the pixel position,
+ * zero in the padding ring like every other channel), BatchNorm, ReLU, the 3x3 convolution cmid -> cmid, BatchNorm, ReLU, and the 2x
+ * bilinear resize (align_corners=False); y [heads][B][2H][2W][cmid].  (cin, cmid) as vp_be_infer_supported() says: (16,4) (4,2) (32,8)
+ * (8,4) (64,16) (16,8), the blocks of MaskNet(16 | 32 | 64).
+ * vp_be_predictor_infer_f32: the three convolutions c -> 2c -> c -> 1 with their biases and no activation (models/networks_BE.py:48-52)
+ * in ONE launch, c = 2 | 4 | 8; logits [heads][B][H][W]; mask (may be NULL) [heads][B][H][W] bytes = logit >= threshold
+ * (test_BE.py:35-39 thresholds the raw output).
+ * The pack kernels build one head's parameter block (vp_be_*_params_floats() floats; head h's block starts h blocks in) from the
+ * reference-layout tensors: the BatchNorms fold as vp_bn_fold_f32 does (fp64, rounded once), the scale INTO the weights, the shift as
+ * the sum's first term.  vp_be_fold_conv_f32 does the same for a BatchNorm-ed convolution that runs on the MFMA kernels (aux_convs):
+ * w_out [cout][cols] = w s, shift [cout].  16-byte aligned operands. */
+int vp_be_infer_supported(int cin, int cmid);
+size_t vp_be_up_params_floats(int cin, int cmid);
+size_t vp_be_predictor_params_floats(int c);
+int vp_be_up_pack_f32(const float* w1, const float* gamma1, const float* beta1, const float* mean1, const float* var1, const float* w2,
+                      const float* gamma2, const float* beta2, const float* mean2, const float* var2, float eps, float* params, int cin,
+                      int cmid, vp_stream stream);
+int vp_be_predictor_pack_f32(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                             float* params, int c, vp_stream stream);
+int vp_be_fold_conv_f32(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, float* w_out,
+                        float* shift, int cout, int cols, vp_stream stream);
+int vp_be_up_infer_f32(const float* x, size_t x_head_stride, const float* params, float* y, int heads, int B, int H, int W, int cin, int cmid,
+                       vp_stream stream);
+int vp_be_predictor_infer_f32(const float* x, size_t x_head_stride, const float* params, float* logits, unsigned char* mask, float threshold,
+                              int heads, int B, int H, int W, int c, vp_stream stream);
 
 /* ---- SCSEBlock (models/blocks.py:52-65), fp32 NHWC, forward and backward ------------------------------------------------------
  * y[b,p,ch] = x (c[b,ch] + s[b,p]) with the channel gate c = sigmoid(W2 relu(W1 mean_p(x) + b1) + b2) (W1 [C/r][C], W2 [C][C/r], the

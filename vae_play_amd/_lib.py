@@ -173,6 +173,14 @@ SIGNATURES = {
     "vp_disc_tap_eval_f32": (c_int, [P, P, P, c_int, c_int, P, P, c_int, P, P]),
     "vp_disc_head_eval_f32": (c_int, [P, P, P, P, P, c_int, c_int, P, P, P, P, P]),
     "vp_lin_fold_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P]),
+    "vp_be_infer_supported": (c_int, [c_int, c_int]),
+    "vp_be_up_params_floats": (c_size_t, [c_int, c_int]),
+    "vp_be_predictor_params_floats": (c_size_t, [c_int]),
+    "vp_be_up_pack_f32": (c_int, [P] * 10 + [c_float, P, c_int, c_int, P]),
+    "vp_be_predictor_pack_f32": (c_int, [P] * 7 + [c_int, P]),
+    "vp_be_fold_conv_f32": (c_int, [P] * 5 + [c_float, P, P, c_int, c_int, P]),
+    "vp_be_up_infer_f32": (c_int, [P, c_size_t, P, P] + [c_int] * 6 + [P]),
+    "vp_be_predictor_infer_f32": (c_int, [P, c_size_t, P, P, P, c_float] + [c_int] * 5 + [P]),
     "vp_scse_workspace_bytes": (c_size_t, [c_int] * 4),
     "vp_scse_fwd_f32": (c_int, [P] * 12 + [c_int] * 5 + [P, c_size_t, P]),
     "vp_scse_bwd_f32": (c_int, [P] * 16 + [c_int] * 5 + [P, c_size_t, P]),

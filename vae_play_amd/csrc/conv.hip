@@ -36,7 +36,7 @@ int vp_conv_gather_f32(const float* big, const float* w_p0, const float* bias, f
   VP_REQUIRE(big && w_p0 && small_out, "vp_conv_gather_f32: null pointer");
   int rc = conv_check("vp_conv_gather_f32", B, Hs, Ws, Hb, Wb, Cbig, Csmall, ks, stride);
   if (rc) return rc;
-  VP_REQUIRE(act == VP_ACT_NONE || act == VP_ACT_SIGMOID, "vp_conv_gather_f32: epilogue supports none|sigmoid");
+  VP_REQUIRE(act == VP_ACT_NONE || act == VP_ACT_SIGMOID || act == VP_ACT_RELU, "vp_conv_gather_f32: epilogue supports none|sigmoid|relu");
   ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
   if (narrow_gather_applicable(g, act)) return narrow_gather_launch(big, w_p0, bias, small_out, g, act, (hipStream_t)stream);
   const ConvPlan pl = plan_conv(false, g, F32, bias != nullptr, act, aligned16(big, w_p0), EPI_NONE, plan_switches());

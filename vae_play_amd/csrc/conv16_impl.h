@@ -53,7 +53,7 @@ static int gather16(const char* what, const void* big_split, const void* w_p0_sp
   VP_REQUIRE(B > 0 && Hs > 0 && Ws > 0 && Cbig > 0 && Csmall > 0 && Cbig % 8 == 0, "%s: Cbig must be a multiple of 8", what);
   VP_REQUIRE(stride == 1 || stride == 2, "%s: stride must be 1 or 2", what);
   VP_REQUIRE(ks == 1 || ks == 3 || ks == 4 || ks == 5, "%s: kernel size must be 1, 3, 4 or 5", what);
-  VP_REQUIRE(act == VP_ACT_NONE || act == VP_ACT_SIGMOID, "%s: epilogue supports none|sigmoid", what);
+  VP_REQUIRE(act == VP_ACT_NONE || act == VP_ACT_SIGMOID || act == VP_ACT_RELU, "%s: epilogue supports none|sigmoid|relu", what);
   if constexpr (F16 != 0) VP_REQUIRE(alpha > 0.f, "%s: out_scale must be positive", what);
   const ConvGeom g = make_geom(B, Hs, Ws, Csmall, Cbig, stride, ks, Hb, Wb);
   const ConvPlan pl = plan_conv(false, g, arith16<F16>(), bias != nullptr, act, true, EPI_NONE, plan_switches());

@@ -13,7 +13,7 @@ constexpr unsigned FORMS_ALL = K64F | K32F | K64S | K32S, TILES_ALL = T_SQUARE |
 // What the epilogue does beyond storing the accumulators; a default-constructed one is "nothing".
 struct ConvEpi {
   const float* bias = nullptr;      // per output channel (scatter family: the generic-geometry descriptors only)
-  int act = VP_ACT_NONE;            // gather: none | sigmoid; affine descriptors: none | relu
+  int act = VP_ACT_NONE;            // gather: none | sigmoid | relu; affine descriptors: none | relu
   float alpha = 1.f;                // multiplies the accumulators (fp16 planes: undoes a producer's scale)
   float* stat = nullptr;            // BatchNorm statistics slab (igemm16.h epilogue_stats32): K must not be split
   const float* scale = nullptr; const float* shift = nullptr; void* out_split = nullptr;      // is_affine<P> only (igemm16.h AffineEpi)

@@ -289,6 +289,7 @@ __global__ void __launch_bounds__(256) halo_conv_kernel(const HaloArgs a) {
         const int y = ty * C::TH + (m >> 4), x = tx * C::TW + (m & 15);
         float v = acc[i][j][r] + bv;
         if (a.act == ACT_SIGMOID) v = 1.f / (1.f + __builtin_expf(-v));
+        else if (a.act == ACT_RELU) v = __builtin_fmaxf(v, 0.f);
         a.out[((size_t)(b * a.Ho + y) * a.Wo + x) * a.N + n] = v;
       }
   }

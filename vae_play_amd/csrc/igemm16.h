@@ -174,6 +174,7 @@ struct ProbF16T {
 #endif
     if (bias) v += bias[n];
     if (act == ACT_SIGMOID) v = 1.f / (1.f + __builtin_expf(-v));
+    else if (act == ACT_RELU) v = __builtin_fmaxf(v, 0.f);
     out[(size_t)m * N + n] = v;
   }
 };

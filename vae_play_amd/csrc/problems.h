@@ -184,6 +184,7 @@ struct ProbF {
     if (m >= M || n >= N) return;
     if (bias) v += bias[n];
     if (act == ACT_SIGMOID) v = 1.f / (1.f + __builtin_expf(-v));
+    else if (act == ACT_RELU) v = __builtin_fmaxf(v, 0.f);
     out[(size_t)m * N + n] = v;
   }
 };

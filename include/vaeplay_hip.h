@@ -597,6 +597,45 @@ int vp_be_up_infer_f32(const float* x, size_t x_head_stride, const float* params
 int vp_be_predictor_infer_f32(const float* x, size_t x_head_stride, const float* params, float* logits, unsigned char* mask, float threshold,
                               int heads, int B, int H, int W, int c, vp_stream stream);
 
+/* ---- inference: the font U-Net, models/networks_BE_font.py ComposeNet in eval mode (csrc/font_infer.hip) ------------
+ * vp_conv_in_act_f32: nn.Conv2d(Cin, Cout, ks, stride, padding=(ks-1)/2, bias=False) + nn.InstanceNorm2d(eps) + activation in ONE
+ * launch, exact fp32 (v_mfma_f32_16x16x4_f32), for layers whose whole output map fits a 256-row tile.  x NHWC [B][H][W][Cin]; output
+ * map Ho x Wo; y[b][p][n] at y + (b*Ho*Wo + p)*ldy + n (ldy >= Cout: y may be a channel slice of a wider NHWC buffer, nothing outside
+ * the slice is written); w_packed [Cout][ks*ks][Cin] written by vp_conv_in_pack_f32 from the reference (Cout,Cin,ks,ks) weight.  A
+ * workgroup owns 256 / (Ho*Wo) whole images and 16 output channels; per (image, channel): mean over the image's rows, biased variance
+ * as the mean of squared deviations from that mean, rstd = 1/sqrt(var + eps), y = act((acc - mean) rstd), act none | relu | lrelu.
+ * Image slots of a tile past B are neither read nor written; a result does not depend on the slot or tile its image sits in.
+ * vp_conv_in_supported (host only) is the single statement of what the kernel takes: (ks, stride) (3,1) (3,2) (1,1); Ho*Wo 16, 64 or
+ * 256 with H, W <= 64; Cin and Cout multiples of 64 up to 1024.  The kernel entry returns VP_ERR_ARG for everything else, and for a
+ * null or misaligned (16-byte) x / w_packed, B <= 0, ldy < Cout, another act, and launches nothing.
+ * vp_conv_in_preferred (host only) is the subset a plan should use it for: the supported layers with ks*ks*Cin <= 576, where it was
+ * measured faster than the convolution + InstanceNorm pair it replaces (DESIGN.md 11.1 has the table). */
+int vp_conv_in_supported(int H, int W, int Cin, int Cout, int ks, int stride);
+int vp_conv_in_preferred(int H, int W, int Cin, int Cout, int ks, int stride);
+int vp_conv_in_pack_f32(const float* w_ref, float* w_packed, int Cout, int Cin, int ks, vp_stream stream);
+int vp_conv_in_act_f32(const float* x, const float* w_packed, float* y, int ldy, int B, int H, int W, int Cin, int Cout, int ks, int stride,
+                       float eps, int act, float slope, vp_stream stream);
+/* The heads' output stage: `heads` Conv2d(C, 1, 3) + bias layers (predictor.2 of edge_net / mask_net) over [heads][B][H][W][C] maps
+ * (x_head_stride floats between two heads' maps) in ONE launch; logits [heads][B][H][W]; mask (may be NULL) bytes = logit >= threshold
+ * (test_BE_font.py:27-31).  C a multiple of 4 up to 256; head h's parameter block ([9][C] weights, bias; vp_font_pred_params_floats(C)
+ * floats, 0 for an unsupported C) starts h blocks in and is written by vp_font_pred_pack_f32 from the (1,C,3,3) weight and the bias. */
+size_t vp_font_pred_params_floats(int C);
+int vp_font_pred_pack_f32(const float* w, const float* bias, float* params, int C, vp_stream stream);
+int vp_font_pred_infer_f32(const float* x, size_t x_head_stride, const float* params, float* logits, unsigned char* mask, float threshold,
+                           int heads, int B, int H, int W, int C, vp_stream stream);
+/* relay_convs.0's input (models/networks_BE_font.py:214-216): out [B][C*HW + 2E] = [map in (C,H,W) order | label | style] from the
+ * NHWC map [B][HW][C] and the two embeddings [B][E]. */
+int vp_font_relay_input_f32(const float* map_nhwc, const float* label, const float* style, float* out, int B, int HW, int C, int E,
+                            vp_stream stream);
+/* SelfAttentionBlock on a 1 x 1 map (models/blocks.py:77-96; the softmax over one position is 1): out = gamma[0] relu(v_pre) + x. */
+int vp_font_attn1_f32(const float* v_pre, const float* x, const float* gamma, float* out, size_t n, vp_stream stream);
+/* Output-row-stride forms of two existing passes, for producers that write their channel slice of a concatenation's input directly:
+ * y row r (an output pixel) starts at y + r*ldy, ldy >= C.  Same arithmetic as vp_upsample2x_bilinear_fwd_f32 /
+ * vp_instnorm_act_fwd_f32 (the latter: C % 4 == 0, ldy % 4 == 0, y 16-byte aligned). */
+int vp_upsample2x_bilinear_fwd_ld_f32(const float* x, float* y, int ldy, int B, int H, int W, int C, vp_stream stream);
+int vp_instnorm_act_fwd_ld_f32(const float* x, float* y, int ldy, float* mean, float* rstd, int B, int R, int C, float eps, int act,
+                               float slope, void* ws, size_t ws_bytes, vp_stream stream);
+
 /* ---- SCSEBlock (models/blocks.py:52-65), fp32 NHWC, forward and backward ------------------------------------------------------
  * y[b,p,ch] = x (c[b,ch] + s[b,p]) with the channel gate c = sigmoid(W2 relu(W1 mean_p(x) + b1) + b2) (W1 [C/r][C], W2 [C][C/r], the
  * 1x1 nn.Conv2d weights of cSE.1 / cSE.3 as they are stored) and the spatial gate s = sigmoid(sum_ch w_s[ch] x[b,p,ch] + b_s) (sSE.0);

@@ -181,6 +181,17 @@ SIGNATURES = {
     "vp_be_fold_conv_f32": (c_int, [P] * 5 + [c_float, P, P, c_int, c_int, P]),
     "vp_be_up_infer_f32": (c_int, [P, c_size_t, P, P] + [c_int] * 6 + [P]),
     "vp_be_predictor_infer_f32": (c_int, [P, c_size_t, P, P, P, c_float] + [c_int] * 5 + [P]),
+    "vp_conv_in_supported": (c_int, [c_int] * 6),
+    "vp_conv_in_preferred": (c_int, [c_int] * 6),
+    "vp_conv_in_pack_f32": (c_int, [P, P, c_int, c_int, c_int, P]),
+    "vp_conv_in_act_f32": (c_int, [P, P, P] + [c_int] * 8 + [c_float, c_int, c_float, P]),
+    "vp_font_pred_params_floats": (c_size_t, [c_int]),
+    "vp_font_pred_pack_f32": (c_int, [P, P, P, c_int, P]),
+    "vp_font_pred_infer_f32": (c_int, [P, c_size_t, P, P, P, c_float] + [c_int] * 5 + [P]),
+    "vp_font_relay_input_f32": (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, P]),
+    "vp_font_attn1_f32": (c_int, [P, P, P, P, c_size_t, P]),
+    "vp_upsample2x_bilinear_fwd_ld_f32": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    "vp_instnorm_act_fwd_ld_f32": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_float, c_int, c_float, P, c_size_t, P]),
     "vp_scse_workspace_bytes": (c_size_t, [c_int] * 4),
     "vp_scse_fwd_f32": (c_int, [P] * 12 + [c_int] * 5 + [P, c_size_t, P]),
     "vp_scse_bwd_f32": (c_int, [P] * 16 + [c_int] * 5 + [P, c_size_t, P]),

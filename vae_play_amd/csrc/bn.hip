@@ -332,10 +332,11 @@ __global__ void act_bwd_from_y_kernel(const float* __restrict__ y, const float* 
 __global__ void __launch_bounds__(256) bn_act_fwd_tiled_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float* __restrict__ y,
-                                                               u16_t* __restrict__ y_split, int R, int C, int rows_per_chunk,
-                                                               int act, float slope, size_t bxs, int sfmt) {
+                                                               u16_t* __restrict__ y_split, int ldy, int R, int C,
+                                                               int rows_per_chunk, int act, float slope, size_t bxs, int sfmt) {
+  // ldy = floats between two rows of y (C: dense; more: y is a channel slice of a wider NHWC buffer); the planes stay dense
   x += blockIdx.z * bxs; mean += blockIdx.z * (size_t)C; rstd += blockIdx.z * (size_t)C;
-  if (y) y += blockIdx.z * bxs;
+  if (y) y += blockIdx.z * (size_t)R * ldy;
   const int tx = threadIdx.x % BN_TX, ty = threadIdx.x / BN_TX;
   const int c = blockIdx.y * BN_CH + tx * 4;
   if (c >= C) return;
@@ -352,7 +353,7 @@ __global__ void __launch_bounds__(256) bn_act_fwd_tiled_kernel(const float* __re
       vp_f32x4 o;
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[j] = act_apply(bn_pre(v.v[0][j], k.mu[j], k.rs[j], k.ga[j], k.be[j]), act, slope);
-      if (y) *reinterpret_cast<vp_f32x4*>(y + off) = o;
+      if (y) *reinterpret_cast<vp_f32x4*>(y + (size_t)r * ldy + c) = o;
       if (y_split) store_split4(y_split, n, off, o[0], o[1], o[2], o[3], sfmt);
     });
 }
@@ -782,12 +783,12 @@ static int launch_bn_bwd_sums(const char* name, const float* x, const float* dy,
 // Apply passes: the tiled kernel for C % 4 == 0, else the flat one (the callers have refused split planes there).  The caller checks
 // the launch.
 static void launch_apply_fwd(const float* x, const float* mean, const float* rstd, const float* gamma, const float* beta, float* y,
-                             void* y_split, int B, int R, int C, int act, float slope, int fmt, hipStream_t s) {
+                             void* y_split, int B, int R, int C, int act, float slope, int fmt, hipStream_t s, int ldy = 0) {
   const size_t bxs = (size_t)R * C;
   if (C % 4 == 0) {
     const BnGrid g = bn_apply_grid(R, C);
     hipLaunchKernelGGL(bn_act_fwd_tiled_kernel, dim3(g.chunks_r, g.chunks_c, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, y,
-                       (u16_t*)y_split, R, C, g.rows_per_chunk, act, slope, bxs, fmt);
+                       (u16_t*)y_split, ldy ? ldy : C, R, C, g.rows_per_chunk, act, slope, bxs, fmt);
   } else {
     hipLaunchKernelGGL(bn_act_fwd_kernel, dim3(grid_for(bxs / 4 + 1, 256), 1, B), dim3(256), 0, s, x, mean, rstd, gamma, beta, y, bxs, C,
                        act, slope, bxs);
@@ -897,15 +898,23 @@ int vp_bn_act_bwd_split_f32(const float* x, const float* dy, const float* mean, 
 size_t vp_instnorm_workspace_bytes(int B, int R, int C) { return bn_ws_bytes(B, R, C); }
 
 static int instnorm_act_fwd_impl(const float* x, float* y, void* y_split, float* mean, float* rstd, int B, int R, int C, float eps, int act,
-                                 float slope, void* ws, size_t ws_bytes, vp_stream stream) {
+                                 float slope, void* ws, size_t ws_bytes, vp_stream stream, int ldy = 0) {
   VP_REQUIRE(x && y && mean && rstd && ws && B > 0 && R > 0 && C > 0, "vp_instnorm_act_fwd_f32: bad arguments");
   VP_REQUIRE(!y_split || C % 4 == 0, "vp_instnorm_act_fwd_split_f32: C must be a multiple of 4");
+  VP_REQUIRE(!ldy || (C % 4 == 0 && ldy % 4 == 0 && ldy >= C && aligned16(y)),
+             "vp_instnorm_act_fwd_ld_f32: C and ldy must be multiples of 4, ldy >= C, y 16-byte aligned");
   if (ws_bytes < vp_instnorm_workspace_bytes(B, R, C)) return fail(VP_ERR_WORKSPACE, "vp_instnorm_act_fwd_f32: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   int rc = launch_stats("vp_instnorm_act_fwd_f32", x, B, R, C, eps, 0.f, mean, rstd, nullptr, nullptr, ws, s);
   if (rc) return rc;
-  launch_apply_fwd(x, mean, rstd, nullptr, nullptr, y, y_split, B, R, C, act, slope, SPLIT_BF16, s);
+  launch_apply_fwd(x, mean, rstd, nullptr, nullptr, y, y_split, B, R, C, act, slope, SPLIT_BF16, s, ldy);
   return check_launch("vp_instnorm_act_fwd_f32(apply)");
+}
+
+int vp_instnorm_act_fwd_ld_f32(const float* x, float* y, int ldy, float* mean, float* rstd, int B, int R, int C, float eps, int act,
+                               float slope, void* ws, size_t ws_bytes, vp_stream stream) {
+  VP_REQUIRE(ldy > 0, "vp_instnorm_act_fwd_ld_f32: ldy must be positive");
+  return instnorm_act_fwd_impl(x, y, nullptr, mean, rstd, B, R, C, eps, act, slope, ws, ws_bytes, stream, ldy);
 }
 
 int vp_instnorm_act_fwd_f32(const float* x, float* y, float* mean, float* rstd, int B, int R, int C, float eps, int act,

@@ -464,12 +464,14 @@ __device__ __forceinline__ void bilin_src(int o, int in_size, int& i0, int& i1, 
   lam = src - (float)i0;
 }
 
-__global__ void upsample2x_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int B, int H, int W, int C) {
+// y row (output pixel) stride ldy >= C: ldy > C writes a channel slice of a wider NHWC buffer (a concatenation's input)
+__global__ void upsample2x_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int ldy, int B, int H, int W, int C) {
   const int Ho = 2 * H, Wo = 2 * W;
   const size_t n = (size_t)B * Ho * Wo * C;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const int c = (int)(i % C);
-    size_t r = i / C;
+    const size_t pix = i / C;
+    size_t r = pix;
     const int ow = (int)(r % Wo); r /= Wo;
     const int oh = (int)(r % Ho);
     const int b = (int)(r / Ho);
@@ -479,7 +481,7 @@ __global__ void upsample2x_fwd_kernel(const float* __restrict__ x, float* __rest
     const float* xb = x + (size_t)b * H * W * C + c;
     const float v00 = xb[((size_t)h0 * W + w0) * C], v01 = xb[((size_t)h0 * W + w1) * C];
     const float v10 = xb[((size_t)h1 * W + w0) * C], v11 = xb[((size_t)h1 * W + w1) * C];
-    y[i] = (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
+    y[pix * ldy + c] = (1.f - lh) * ((1.f - lw) * v00 + lw * v01) + lh * ((1.f - lw) * v10 + lw * v11);
   }
 }
 
@@ -761,7 +763,13 @@ int vp_bce_sigmoid_bwd_pad_split_f32(const float* p, const float* t, float gscal
 int vp_upsample2x_bilinear_fwd_f32(const float* x, float* y, int B, int H, int W, int C, vp_stream stream) {
   VP_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0, "vp_upsample2x_bilinear_fwd_f32: bad arguments");
   return launch_flat("vp_upsample2x_bilinear_fwd_f32", upsample2x_fwd_kernel, (size_t)B * 4 * H * W * C, FLAT_CAP, (hipStream_t)stream, x,
-                     y, B, H, W, C);
+                     y, C, B, H, W, C);
+}
+
+int vp_upsample2x_bilinear_fwd_ld_f32(const float* x, float* y, int ldy, int B, int H, int W, int C, vp_stream stream) {
+  VP_REQUIRE(x && y && B > 0 && H > 0 && W > 0 && C > 0 && ldy >= C, "vp_upsample2x_bilinear_fwd_ld_f32: bad arguments (ldy >= C)");
+  return launch_flat("vp_upsample2x_bilinear_fwd_ld_f32", upsample2x_fwd_kernel, (size_t)B * 4 * H * W * C, FLAT_CAP, (hipStream_t)stream,
+                     x, y, ldy, B, H, W, C);
 }
 
 int vp_upsample2x_bilinear_bwd_f32(const float* dy, float* dx, int B, int H, int W, int C, vp_stream stream) {

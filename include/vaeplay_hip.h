@@ -676,6 +676,36 @@ int vp_twin_head_bwd_f32(const float* h_adv, const float* h_aux, const float* w_
                          const float* aux, const float* d_adv, const float* d_aux, float* dh_adv, float* dh_aux, float* dw_adv,
                          float* db_adv, float* dw_aux, float* db_aux, int B, int C, int K, vp_stream stream);
 
+/* ---- inference: the Style-GAN row, models/network_Style_GAN.py under torch.no_grad() (csrc/stylegan_infer.hip) ------
+ * vp_scse2_fwd_f32: y = relu?(SCSE_b(SCSE_a(x))), two SCSEBlocks of the same C and hidden = C / reduction one after the other (the
+ * tail of StyleUp.cat_convs, :54-59), fp32 NHWC [B][HW][C], each block as vp_scse_fwd_f32 defines it; parameters of block a then of
+ * block b, as the 1x1 nn.Conv2d weights are stored.  Block a's spatial gate needs no pooling, so block b's pooled input is
+ * c_a mean_p(x) + mean_p(x s_a): the call reads x twice and writes y once (two vp_scse_fwd_f32 calls: four reads, two writes) and
+ * leaves nothing for a backward call (no pool, hid, cgate, sgate).  y_split (may be NULL; needs C % 8 == 0 and the 16-byte path): the
+ * bf16 hi/lo planes of y, plane = B*HW*C elements, laid out as by vp_instnorm_act_fwd_split_f32 and equal to vp_split_f32 of y.
+ * Ranges, paths and status codes are vp_scse_fwd_f32's: C <= 1024 when C % 4 == 0 and x, y, w_sa, w_sb, ws are 16-byte aligned, else
+ * the scalar path for C <= 256; 1 <= hidden <= C; VP_ERR_ARG for anything else or a null pointer, VP_ERR_WORKSPACE for fewer than
+ * vp_scse2_workspace_bytes() bytes; a refused call launches nothing.  Fixed-order sums, no atomics: two runs give the same bits.
+ * vp_scse2_preferred (host only): the shapes a plan should take it for over two vp_scse_fwd_f32 calls: C % 4 == 0.
+ * vp_cat2_nhwc_f32: out [B][HW][Ca + Cb] = the channel concatenation of a and b; a source is [B][C][HW] (flag 0, NCHW) or
+ * [B][HW][C] (flag 1, NHWC).  The generator's input (image, 3 | style plane, 1) and the discriminator's (x, 3 | x_content, 3).
+ * vp_sg_out_tanh_f32: Generator.final.3 + tanh (:116-124): out [B][3][H][W] (NCHW) = tanh(Conv2d(C, 3, 3, padding 1)(x) + bias) of
+ * the NHWC map x [B][H][W][C], exact fp32, one launch.  C a multiple of 4 up to 256; x and params 16-byte aligned; params
+ * ([3][9][C] weights, 3 biases, a zero; vp_sg_out_params_floats(C) floats, 0 for an unsupported C) is written by vp_sg_out_pack_f32
+ * from the (3, C, 3, 3) weight and the bias.  vp_sg_out_tanh_preferred (host only): where a plan should take it over the
+ * convolution, vp_act_fwd_f32 and vp_nhwc_to_nchw_f32 launches it replaces: C = 32, the width it was measured at. */
+size_t vp_scse2_workspace_bytes(int B, int HW, int C, int hidden);
+int vp_scse2_preferred(int B, int HW, int C, int hidden);
+int vp_scse2_fwd_f32(const float* x, const float* w1a, const float* b1a, const float* w2a, const float* b2a, const float* w_sa,
+                     const float* b_sa, const float* w1b, const float* b1b, const float* w2b, const float* b2b, const float* w_sb,
+                     const float* b_sb, float* y, void* y_split, int B, int HW, int C, int hidden, int relu, void* ws, size_t ws_bytes,
+                     vp_stream stream);
+int vp_cat2_nhwc_f32(const float* a, int a_nhwc, const float* b, int b_nhwc, float* out, int B, int HW, int Ca, int Cb, vp_stream stream);
+size_t vp_sg_out_params_floats(int C);
+int vp_sg_out_tanh_preferred(int B, int H, int W, int C);
+int vp_sg_out_pack_f32(const float* w, const float* bias, float* params, int C, vp_stream stream);
+int vp_sg_out_tanh_f32(const float* x, const float* params, float* out, int B, int H, int W, int C, vp_stream stream);
+
 /* ---- optimiser step on a flat arena (train_BE.py:62-64,131; train.py:136-140) --------------- */
 /* torch.optim.Adam semantics (no amsgrad, no weight decay); g is multiplied by grad_scale first
  * (1/world_size after a sum all-reduce). step is the 1-based step count. */

@@ -12,8 +12,10 @@ from .infer import FusedVAEInference  # noqa: F401
 from .infer_gan import FusedVAEGANInference  # noqa: F401
 from .infer_be import FusedBEInference  # noqa: F401
 from .infer_font import FusedFontInference  # noqa: F401
+from .infer_stylegan import FusedStyleGanInference  # noqa: F401
 
 __all__ = ["VAE", "VaeGan", "Encoder", "Decoder", "Discriminator", "DirectDecoder", "EncoderBlock", "DecoderBlock",
            "reparameterize", "init_parameters",
            "binary_cross_entropy", "kl_divergence", "vae_loss", "set_conv_precision", "get_conv_precision",
-           "FusedVAEInference", "FusedVAEGANInference", "FusedBEInference", "FusedFontInference"]
+           "FusedVAEInference", "FusedVAEGANInference", "FusedBEInference", "FusedFontInference",
+           "FusedStyleGanInference"]

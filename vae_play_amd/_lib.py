@@ -197,6 +197,14 @@ SIGNATURES = {
     "vp_scse_bwd_f32": (c_int, [P] * 16 + [c_int] * 5 + [P, c_size_t, P]),
     "vp_twin_head_fwd_f32": (c_int, [P] * 8 + [c_int] * 3 + [P]),
     "vp_twin_head_bwd_f32": (c_int, [P] * 14 + [c_int] * 3 + [P]),
+    "vp_scse2_workspace_bytes": (c_size_t, [c_int] * 4),
+    "vp_scse2_preferred": (c_int, [c_int] * 4),
+    "vp_scse2_fwd_f32": (c_int, [P] * 15 + [c_int] * 5 + [P, c_size_t, P]),
+    "vp_cat2_nhwc_f32": (c_int, [P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, P]),
+    "vp_sg_out_params_floats": (c_size_t, [c_int]),
+    "vp_sg_out_tanh_preferred": (c_int, [c_int] * 4),
+    "vp_sg_out_pack_f32": (c_int, [P, P, P, c_int, P]),
+    "vp_sg_out_tanh_f32": (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
     "vp_adam_f32": (c_int, [P, P, P, P, c_size_t, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "vp_adam_outer_f32": (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "vp_rmsprop_f32": (c_int, [P, P, P, c_size_t, c_float, c_float, c_float, c_float, P]),

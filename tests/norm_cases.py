@@ -38,14 +38,21 @@ class Lib:
             raise RuntimeError(f"{name} failed (status {rc}): {(self.h.vp_last_error() or b'').decode()}")
 
 
-def inputs(B, R, C, seed=0):
-    """x [B][R][C] with |mean| >> sigma per channel, dy, gamma, beta [C], label [B], on the device"""
+OFFSET_BATCHED = [(3, 65, 68), (3, 200, 6)]   # InstanceNorm with inputs(..., offset=OFFSET): every image far from the others
+OFFSET = 300.0
+
+
+def inputs(B, R, C, seed=0, offset=0.0, device="cuda"):
+    """x [B][R][C] with |mean| >> sigma per channel, dy, gamma, beta [C], label [B], on the device.  offset adds offset * randn per
+    image and channel to x, drawn after everything else: a statistic, pivot or slab taken from another image is then far off."""
     g = torch.Generator().manual_seed(seed * 1000003 + B * 7919 + R * 131 + C)
     x = torch.randn(B, R, C, generator=g) * 1.5 + torch.randn(1, 1, C, generator=g) * 20
     dy = torch.randn(B, R, C, generator=g)
     gamma, beta = torch.rand(C, generator=g) + 0.5, torch.randn(C, generator=g) * 0.3
     label = torch.rand(B, generator=g)
-    return [t.cuda() for t in (x, dy, gamma, beta, label)]
+    if offset:
+        x = x + offset * torch.randn(B, 1, C, generator=g)
+    return [t.to(device) for t in (x, dy, gamma, beta, label)]
 
 
 def _ps():
@@ -136,6 +143,16 @@ def inorm_fwd(L, G, x, B, R, C, act, split=False):
     else:
         L.call("vp_instnorm_act_fwd_f32", P(x), P(y), P(mean), P(rstd), B, R, C, EPS, act, SLOPE, P(ws), nb, st)
     return y, mean, rstd, ys
+
+
+def inorm_fwd_ld(L, G, x, B, R, C, act, ldy, col):
+    """y as columns [col, col + C) of a NaN-filled [B][R][ldy] buffer -> the whole buffer, mean [B][C], rstd [B][C]"""
+    P, _, st = _ps()
+    wide = G.ws("y_wide", B * R * ldy * 4)[0].view(B, R, ldy)          # the columns outside the slice keep their NaN
+    mean, rstd = G.out("mean", B, C), G.out("rstd", B, C)
+    ws, nb = G.ws("ws", L.h.vp_instnorm_workspace_bytes(B, R, C))
+    L.call("vp_instnorm_act_fwd_ld_f32", P(x), P(wide[0, 0, col:]), ldy, P(mean), P(rstd), B, R, C, EPS, act, SLOPE, P(ws), nb, st)
+    return wide, mean, rstd
 
 
 def inorm_bwd(L, G, x, dy, mean, rstd, B, R, C, act, split=False):

@@ -597,6 +597,30 @@ int vp_be_up_infer_f32(const float* x, size_t x_head_stride, const float* params
 int vp_be_predictor_infer_f32(const float* x, size_t x_head_stride, const float* params, float* logits, unsigned char* mask, float threshold,
                               int heads, int B, int H, int W, int c, vp_stream stream);
 
+/* ---- inference: page compositing for the mask / edge heads (csrc/be_page.hip) ---------------------------------------
+ * What the reference's test_BE_manga.py:63-147 (paset_result_on_manga) and :160-225 (paset_edge_result_on_manga) do on the host: the
+ * predictions of a page's m bubble crops pasted into one page [H][W][3] uint8 label map, channels (edge, bubble type, content), bit
+ * for bit.  Bubble i's logit planes are edges + i * edge_stride and masks + i * mask_stride ([SH][SW] fp32 each, strides in floats;
+ * a bit is set unless logit < threshold, so a NaN is set), its page mask page_masks + i * H * W bytes (non-zero = set).
+ * desc: m rows of VP_BE_PAGE_DESC_INTS int32 on the device, 16-byte aligned:
+ *   0..3   anchor_x, anchor_y, the fp32 bits of (float)SW / (float)size, the fp32 bits of (float)SH / (float)size
+ *   4..7   xmin, ymin, xmax, ymax     the bubble's box on the page, half-open
+ *   8..11  rx0, ry0, rx1, ry1         kind 1: the content rectangle in crop coordinates, half-open
+ *   12..15 label (0..255), kind, 0, 0
+ * A page pixel (y, x) inside the box has crop coordinates cy = anchor_y + y - ymin, cx = anchor_x + x - xmin and samples the planes at
+ * min((int)floorf(c * scale), S - 1) per axis (torch's nearest resize of the plane to size x size).  kind 0: edge and content bit from
+ * edges / masks; kind 1: content = inside the rectangle, edge = inside the rectangle grown by 6 (empty for an empty rectangle);
+ * kind 2: content = page mask, edge = OR of the page mask over the 13 x 13 window clipped to the box; kind 3: edge from edges,
+ * content = page mask.  edge &= ~content; the first bubble in table order with either bit claims the pixel: edge (255, label, 0),
+ * content (0, label, 255); unclaimed pixels are (255, 255, 255).  masks may be NULL when no row has kind 0, page_masks when none has
+ * kind 2 or 3, edges when none has kind 0 or 3: the caller vouches for the table, the kernel only keeps its reads inside the planes.
+ * init_white != 0 writes the whole page; 0 continues a page, adding bubbles only where it is still white (a claimed pixel is never
+ * white, so chunk after chunk onto one page equals one call).  One launch, no host synchronisation; H * W <= 2^30. */
+#define VP_BE_PAGE_DESC_INTS 16
+int vp_be_compose_page_u8(const float* edges, size_t edge_stride, const float* masks, size_t mask_stride, const int* desc, int m,
+                          const unsigned char* page_masks, unsigned char* page, int H, int W, int SH, int SW, float threshold,
+                          int init_white, vp_stream stream);
+
 /* ---- inference: the font U-Net, models/networks_BE_font.py ComposeNet in eval mode (csrc/font_infer.hip) ------------
  * vp_conv_in_act_f32: nn.Conv2d(Cin, Cout, ks, stride, padding=(ks-1)/2, bias=False) + nn.InstanceNorm2d(eps) + activation in ONE
  * launch, exact fp32 (v_mfma_f32_16x16x4_f32), for layers whose whole output map fits a 256-row tile.  x NHWC [B][H][W][Cin]; output

@@ -11,6 +11,7 @@ from .functional import (binary_cross_entropy, get_conv_precision, kl_divergence
 from .infer import FusedVAEInference  # noqa: F401
 from .infer_gan import FusedVAEGANInference  # noqa: F401
 from .infer_be import FusedBEInference  # noqa: F401
+from .be_page import compose_page  # noqa: F401
 from .infer_font import FusedFontInference  # noqa: F401
 from .infer_stylegan import FusedStyleGanInference  # noqa: F401
 
@@ -18,4 +19,4 @@ __all__ = ["VAE", "VaeGan", "Encoder", "Decoder", "Discriminator", "DirectDecode
            "reparameterize", "init_parameters",
            "binary_cross_entropy", "kl_divergence", "vae_loss", "set_conv_precision", "get_conv_precision",
            "FusedVAEInference", "FusedVAEGANInference", "FusedBEInference", "FusedFontInference",
-           "FusedStyleGanInference"]
+           "FusedStyleGanInference", "compose_page"]

@@ -181,6 +181,7 @@ SIGNATURES = {
     "vp_be_fold_conv_f32": (c_int, [P] * 5 + [c_float, P, P, c_int, c_int, P]),
     "vp_be_up_infer_f32": (c_int, [P, c_size_t, P, P] + [c_int] * 6 + [P]),
     "vp_be_predictor_infer_f32": (c_int, [P, c_size_t, P, P, P, c_float] + [c_int] * 5 + [P]),
+    "vp_be_compose_page_u8": (c_int, [P, c_size_t, P, c_size_t, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P]),
     "vp_conv_in_supported": (c_int, [c_int] * 6),
     "vp_conv_in_preferred": (c_int, [c_int] * 6),
     "vp_conv_in_pack_f32": (c_int, [P, P, c_int, c_int, c_int, P]),

@@ -12,16 +12,19 @@ For a channels_last input that is ``len(aux_convs) + 3`` launches in an "f32" pl
 than forty.  ``precision`` selects the arithmetic of the ``aux_convs`` layers only -- "f32" (exact fp32 products) or
 "bf16x3" (split-bf16 operands: each layer's input is split first, one more launch per layer); the head kernels are always exact fp32.
 
+``segment_page`` adds the last stage of ``test_BE_manga.py``: each batch chunk's logits are pasted, where they lie in the plan, into the
+page's label map by one more launch (csrc/be_page.hip, ``be_page.compose_page``).
+
 The torchvision backbone is out of scope: the input is its stride-4 feature map.  If the net has one the caller
 runs it: ``inf.predict(net.feature_net.backbone(img)["0"])``.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
-from . import _lib, ops
+from . import _lib, be_page, ops
 from .infer import FusedVAEInference
 from .plan import PlanBuilder, _Plan, _ptr, plan_device
 
@@ -215,3 +218,32 @@ class FusedBEInference:
             if self._graphs:
                 self._graphs.update(self._capture(["segment", "segment.cl"]))
         return self._heads_out(x, "segment", True)
+
+    def segment_page(self, x: torch.Tensor, recon_info, boxes, labels, page_hw, original_boxes=None, page_masks=None,
+                     variant: str = "result", threshold: float = 0.5, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The (H, W, 3) uint8 page label map of ``be_page.compose_page`` for the crops' feature maps x (n, C, feat_h, feat_w), bubble i
+        being row i: every batch chunk runs the ``segment`` launch list and is composed straight from the plan's logit planes onto the
+        one page, so the per-crop outputs are neither copied out nor held for all n.  ``threshold`` is the page's own (the plan's
+        ``segment`` threshold and masks are left alone).  ``n == 0`` gives a white page."""
+        H, W = (int(v) for v in page_hw)
+        n = int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 4 else -1
+        logit_hw = (4 * self.h, 4 * self.w)
+        table = be_page.page_descriptors(recon_info, boxes, labels, (H, W), logit_hw, original_boxes, page_masks is not None, variant)
+        if n >= 0 and table.shape[0] != n:
+            raise ValueError(f"metadata for {table.shape[0]} bubbles, x has {n} rows")
+        if page_masks is not None:
+            be_page.check_page_masks(page_masks, table.shape[0], (H, W))
+            be_page.require_device(page_masks, "page_masks", self.dev)
+        page = be_page.page_buffer(out, (H, W), self.dev)
+        if n == 0:
+            be_page.launch(None, 0, None, 0, None, 0, None, page, logit_hw, threshold, True)
+            return page
+        src, cl, static = self._feed(x)
+        dtab = table.to(self.dev, non_blocking=True)
+        plane = self.logits[0, 0].numel()
+        for i0, m in self._chunks(n):
+            self._load(static, src[i0:i0 + m])
+            self._run("segment" + cl)
+            be_page.launch(_ptr(self.logits[0]), plane, _ptr(self.logits[1]), plane, dtab[i0:], m,
+                           None if page_masks is None else page_masks[i0:], page, logit_hw, threshold, i0 == 0)
+        return page

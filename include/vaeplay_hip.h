@@ -621,6 +621,24 @@ int vp_be_compose_page_u8(const float* edges, size_t edge_stride, const float* m
                           const unsigned char* page_masks, unsigned char* page, int H, int W, int SH, int SW, float threshold,
                           int init_white, vp_stream stream);
 
+/* ---- evaluation of the mask / edge heads (csrc/seg_eval.hip) ----------------------------------------------------------
+ * Per head and image, from logit planes [heads][B][H][W] and target planes of the same shape (fp32, head strides in floats as
+ * vp_be_up_infer_f32 takes x_head_stride; any 4-byte-aligned base, 16-byte loads when W % 4 == 0 and bases and strides allow them).
+ * The reference has no evaluation (it writes overlays); the loss terms are those of train_BE.py:58-59.  Outputs [heads][B][k]:
+ *   sums[4]   {sum bce, sum p t, sum p, sum t}, p = sigmoid(x), bce = max(x, 0) - x t + log1p(exp(-|x|)): vp_be_loss_fwd_f32's
+ *   terms[3]  {sum bce / (H W), dice = (2 sum p t + smooth) / (sum p + sum t + smooth), bce_weight * sum bce / (H W) + 1 - dice};
+ *             the mean of terms[2] over the images of a head is vp_be_loss_fwd_f32's loss
+ *   counts[6] int32 {|P|, |T|, |P & T|, matched_pred, matched_target, nonfinite}: P = (x >= threshold) (a NaN is not in P),
+ *             T = (t >= target_threshold); matched_pred = pixels of P with a pixel of T within Chebyshev distance tol inside the same
+ *             image, matched_target its mirror image (both |P & T| for tol == 0); nonfinite = logits that are NaN or +-inf
+ * tol 0..4, H * W <= 2^24, heads and B <= 65535, finite thresholds; VP_ERR_ARG otherwise, VP_ERR_WORKSPACE for fewer than
+ * vp_seg_eval_workspace_bytes() bytes (0 for shapes the entry refuses); ws 8-byte aligned.  Two launches, fixed-order sums (fp64
+ * partials), no atomics: two runs give the same bits. */
+size_t vp_seg_eval_workspace_bytes(int heads, int B, int H, int W, int tol);
+int vp_seg_eval_f32(const float* logits, size_t logit_head_stride, const float* targets, size_t target_head_stride, float* sums,
+                    float* terms, int* counts, int heads, int B, int H, int W, float threshold, float target_threshold,
+                    float bce_weight, float smooth, int tol, void* ws, size_t ws_bytes, vp_stream stream);
+
 /* ---- inference: the font U-Net, models/networks_BE_font.py ComposeNet in eval mode (csrc/font_infer.hip) ------------
  * vp_conv_in_act_f32: nn.Conv2d(Cin, Cout, ks, stride, padding=(ks-1)/2, bias=False) + nn.InstanceNorm2d(eps) + activation in ONE
  * launch, exact fp32 (v_mfma_f32_16x16x4_f32), for layers whose whole output map fits a 256-row tile.  x NHWC [B][H][W][Cin]; output

@@ -12,6 +12,7 @@ from .infer import FusedVAEInference  # noqa: F401
 from .infer_gan import FusedVAEGANInference  # noqa: F401
 from .infer_be import FusedBEInference  # noqa: F401
 from .be_page import compose_page  # noqa: F401
+from .seg_eval import segmentation_metrics, summarize  # noqa: F401
 from .infer_font import FusedFontInference  # noqa: F401
 from .infer_stylegan import FusedStyleGanInference  # noqa: F401
 
@@ -19,4 +20,4 @@ __all__ = ["VAE", "VaeGan", "Encoder", "Decoder", "Discriminator", "DirectDecode
            "reparameterize", "init_parameters",
            "binary_cross_entropy", "kl_divergence", "vae_loss", "set_conv_precision", "get_conv_precision",
            "FusedVAEInference", "FusedVAEGANInference", "FusedBEInference", "FusedFontInference",
-           "FusedStyleGanInference", "compose_page"]
+           "FusedStyleGanInference", "compose_page", "segmentation_metrics", "summarize"]

@@ -182,6 +182,8 @@ SIGNATURES = {
     "vp_be_up_infer_f32": (c_int, [P, c_size_t, P, P] + [c_int] * 6 + [P]),
     "vp_be_predictor_infer_f32": (c_int, [P, c_size_t, P, P, P, c_float] + [c_int] * 5 + [P]),
     "vp_be_compose_page_u8": (c_int, [P, c_size_t, P, c_size_t, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P]),
+    "vp_seg_eval_workspace_bytes": (c_size_t, [c_int] * 5),
+    "vp_seg_eval_f32": (c_int, [P, c_size_t, P, c_size_t, P, P, P] + [c_int] * 4 + [c_float] * 4 + [c_int, P, c_size_t, P]),
     "vp_conv_in_supported": (c_int, [c_int] * 6),
     "vp_conv_in_preferred": (c_int, [c_int] * 6),
     "vp_conv_in_pack_f32": (c_int, [P, P, c_int, c_int, c_int, P]),

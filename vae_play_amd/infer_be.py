@@ -24,7 +24,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, be_page, ops
+from . import _lib, be_page, ops, seg_eval
 from .infer import FusedVAEInference
 from .plan import PlanBuilder, _Plan, _ptr, plan_device
 
@@ -218,6 +218,24 @@ class FusedBEInference:
             if self._graphs:
                 self._graphs.update(self._capture(["segment", "segment.cl"]))
         return self._heads_out(x, "segment", True)
+
+    def evaluate(self, x: torch.Tensor, edge_targets: torch.Tensor, mask_targets: torch.Tensor, threshold: float = 0.5, tolerance: int = 0,
+                 bce_weight: float = 0.5, smooth: float = 1.0) -> Dict[str, Dict[str, torch.Tensor]]:
+        """{"edges": result, "masks": result}, each the ``seg_eval.segmentation_metrics`` result -- per-image loss terms of
+        train_BE.py:58-59, confusion counts at ``threshold`` (``segment``'s rule), the boundary match within ``tolerance`` pixels -- of
+        the feature maps x against (n, 1, 4 feat_h, 4 feat_w) fp32 targets: every batch chunk runs the ``predict`` launch list and is
+        evaluated where its logits lie in the plan, so nothing is copied out.  ``seg_eval.summarize`` reads a result."""
+        n = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        for t, what in ((edge_targets, "edge_targets"), (mask_targets, "mask_targets")):
+            seg_eval.check_planes(t, what, n or None, (4 * self.h, 4 * self.w))
+        src, cl, static = self._feed(x)
+
+        def chunks():
+            for i0, m in self._chunks(n):
+                self._load(static, src[i0:i0 + m])
+                self._run("predict" + cl)
+                yield i0, m
+        return seg_eval.evaluate_plan(self, n, chunks(), edge_targets, mask_targets, threshold, tolerance, bce_weight, smooth)
 
     def segment_page(self, x: torch.Tensor, recon_info, boxes, labels, page_hw, original_boxes=None, page_masks=None,
                      variant: str = "result", threshold: float = 0.5, out: Optional[torch.Tensor] = None) -> torch.Tensor:

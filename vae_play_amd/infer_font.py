@@ -21,7 +21,7 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _lib, networks_BE_font, ops
+from . import _lib, networks_BE_font, ops, seg_eval
 from .infer import FusedVAEInference
 from .plan import PlanBuilder, _Plan, _ptr, plan_device
 
@@ -347,6 +347,27 @@ class FusedFontInference:
             if self._graphs:
                 self._graphs.update(self._capture([k for k in self._plans if k.startswith("segment")]))
         return self._heads_out(x, y, "segment", True)
+
+    def evaluate(self, x: torch.Tensor, edge_targets: torch.Tensor, mask_targets: torch.Tensor, y: Optional[dict] = None,
+                 threshold: float = 0.5, tolerance: int = 0, bce_weight: float = 0.5, smooth: float = 1.0) -> Dict[str, Dict[str, torch.Tensor]]:
+        """{"edges": result, "masks": result}, each the ``seg_eval.segmentation_metrics`` result -- per-image loss terms of
+        train_BE.py:58-59, confusion counts at ``threshold`` (``segment``'s rule), the boundary match within ``tolerance`` pixels -- of
+        the images x (conditioned as ``predict`` does) against (n, 1, S, S) fp32 targets: every batch chunk runs the ``predict`` launch
+        list and is evaluated where its logits lie in the plan, so nothing is copied out."""
+        if x is None:
+            raise _lib.VaePlayHipError(f"FusedFontInference: x must be a tensor of shape (n, 3, {self.S}, {self.S}) on the HIP device")
+        rows = x.shape[0] if isinstance(x, torch.Tensor) and x.dim() == 4 else 0
+        for t, what in ((edge_targets, "edge_targets"), (mask_targets, "mask_targets")):
+            seg_eval.check_planes(t, what, rows or None, (self.S, self.S))
+        n, suffix, loads = self._feed(x, y)
+
+        def chunks():
+            for i0, m in self._chunks(n):
+                for static, src in loads:
+                    self._load(static, src[i0:i0 + m])
+                self._run("predict" + suffix)
+                yield i0, m
+        return seg_eval.evaluate_plan(self, n, chunks(), edge_targets, mask_targets, threshold, tolerance, bce_weight, smooth)
 
     def condition(self, x: Optional[torch.Tensor] = None, y: Optional[dict] = None):
         """(label, style), each (n, 256): ``embeding_block(y["cls"], y["cnt_style"])`` when ``y`` is given, else ``style_encoder(x, x)``"""

@@ -718,6 +718,28 @@ int vp_twin_head_bwd_f32(const float* h_adv, const float* h_aux, const float* w_
                          const float* aux, const float* d_adv, const float* d_aux, float* dh_adv, float* dh_aux, float* dw_adv,
                          float* db_adv, float* dw_aux, float* db_aux, int B, int C, int K, vp_stream stream);
 
+/* ---- SelfAttentionBlock (models/blocks.py:68-96) without the N x N map, exact fp32, forward and backward (csrc/attention.hip,
+ * DESIGN.md 11.2).  Per image b: q, k [N][dq]; v, x, g [N][C], row-major (the NHWC memory of the block's maps, N = H * W); dq and C are
+ * any positive ints (the block gives dq = C / 8).
+ *   forward    o = softmax_rows(q k^T) v,  y = gamma[0] * o + x,  lse[b][i] = log sum_j exp(q_i . k_j)         one launch
+ *   backward   dq_out, dk_out, dv_out of y against the upstream gradient g (dx = g is the caller's), dgamma[0] = sum g o; the map is
+ *              recomputed from lse, never stored                                                                five launches at most
+ * gamma is read on the device.  o and lse are what the backward call needs besides the inputs (gamma may be 0, so o cannot be had
+ * from y).  dq_out, dk_out, dv_out may each be null: that gradient's kernel is not launched.  The workspace (delta [B][N] and the
+ * partials of dgamma) is vp_attn_bwd_workspace_bytes() bytes, 0 for dims the entry refuses; it grows with B * N alone.
+ * Every output element is written by one lane and dgamma is summed from per-workgroup partials in a fixed order: no atomics, no
+ * hand-off between workgroups, two runs give the same bits.  16-byte loads when dq % 4 == 0 (q, k) resp. C % 4 == 0 (v, g) and the
+ * pointers are 16-byte aligned, 4-byte loads otherwise (same range, same results).
+ * VP_ERR_ARG for a non-positive dim, a null required pointer (everything but the three optional gradients), B > 65535, or
+ * (N + 64) * max(C, dq) >= 2^31 (the kernels index one image with 32 bits); VP_ERR_WORKSPACE for a workspace that is too small.  A
+ * refused call launches nothing. */
+int vp_attn_fwd_f32(const float* q, const float* k, const float* v, const float* x, const float* gamma, float* y, float* o, float* lse,
+                    int B, int N, int dq, int C, vp_stream stream);
+size_t vp_attn_bwd_workspace_bytes(int B, int N, int dq, int C);
+int vp_attn_bwd_f32(const float* q, const float* k, const float* v, const float* o, const float* lse, const float* g,
+                    const float* gamma, float* dq_out, float* dk_out, float* dv_out, float* dgamma, void* ws, size_t ws_bytes, int B,
+                    int N, int dq, int C, vp_stream stream);
+
 /* ---- inference: the Style-GAN row, models/network_Style_GAN.py under torch.no_grad() (csrc/stylegan_infer.hip) ------
  * vp_scse2_fwd_f32: y = relu?(SCSE_b(SCSE_a(x))), two SCSEBlocks of the same C and hidden = C / reduction one after the other (the
  * tail of StyleUp.cat_convs, :54-59), fp32 NHWC [B][HW][C], each block as vp_scse_fwd_f32 defines it; parameters of block a then of

@@ -6,8 +6,8 @@ Importing the package does not touch the GPU; using any op without libvaeplay_hi
 from . import _lib  # noqa: F401
 from .networks import (VAE, Decoder, DecoderBlock, DirectDecoder, Discriminator, Encoder, EncoderBlock,  # noqa: F401
                        VaeGan, init_parameters, reparameterize)
-from .functional import (binary_cross_entropy, get_conv_precision, kl_divergence, set_conv_precision,  # noqa: F401
-                         vae_loss)
+from .functional import (binary_cross_entropy, get_attention_route, get_conv_precision, kl_divergence,  # noqa: F401
+                         set_attention_route, set_conv_precision, vae_loss)
 from .infer import FusedVAEInference  # noqa: F401
 from .infer_gan import FusedVAEGANInference  # noqa: F401
 from .infer_be import FusedBEInference  # noqa: F401
@@ -19,5 +19,6 @@ from .infer_stylegan import FusedStyleGanInference  # noqa: F401
 __all__ = ["VAE", "VaeGan", "Encoder", "Decoder", "Discriminator", "DirectDecoder", "EncoderBlock", "DecoderBlock",
            "reparameterize", "init_parameters",
            "binary_cross_entropy", "kl_divergence", "vae_loss", "set_conv_precision", "get_conv_precision",
+           "set_attention_route", "get_attention_route",
            "FusedVAEInference", "FusedVAEGANInference", "FusedBEInference", "FusedFontInference",
            "FusedStyleGanInference", "compose_page", "segmentation_metrics", "summarize"]

@@ -200,6 +200,9 @@ SIGNATURES = {
     "vp_scse_bwd_f32": (c_int, [P] * 16 + [c_int] * 5 + [P, c_size_t, P]),
     "vp_twin_head_fwd_f32": (c_int, [P] * 8 + [c_int] * 3 + [P]),
     "vp_twin_head_bwd_f32": (c_int, [P] * 14 + [c_int] * 3 + [P]),
+    "vp_attn_fwd_f32": (c_int, [P] * 8 + [c_int] * 4 + [P]),
+    "vp_attn_bwd_workspace_bytes": (c_size_t, [c_int] * 4),
+    "vp_attn_bwd_f32": (c_int, [P] * 12 + [c_size_t] + [c_int] * 4 + [P]),
     "vp_scse2_workspace_bytes": (c_size_t, [c_int] * 4),
     "vp_scse2_preferred": (c_int, [c_int] * 4),
     "vp_scse2_fwd_f32": (c_int, [P] * 15 + [c_int] * 5 + [P, c_size_t, P]),

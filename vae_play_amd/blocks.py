@@ -149,7 +149,9 @@ class Up(nn.Module):
 
 class SelfAttentionBlock(nn.Module):
     """models/blocks.py:66-96: keys q.conv.0.*, k.conv.0.*, v.conv.0.*, gamma.  (The reference builds q/k/v with its
-    ``Conv2d`` block's default activation, so they end in a ReLU; reproduced.)"""
+    ``Conv2d`` block's default activation, so they end in a ReLU; reproduced.)  The attention itself is functional.self_attention:
+    for H*W > 1 one flash-style HIP launch forward for the whole batch and at most five backward, without the (B, N, N) map
+    (``vae_play_amd.set_attention_route`` selects the earlier per-image GEMM route); H*W = 1 short-circuits."""
 
     def __init__(self, in_channel):
         super().__init__()

@@ -14,6 +14,7 @@ Reference ops replaced (relative to the reference checkout):
   reparameterize     VaeGan.reparameterize                      models/networks.py:228-231
   kl_divergence      VaeGan.loss (kl term)                      models/networks.py:270
   binary_cross_entropy  F.binary_cross_entropy                  train_BE_font.py:107
+  self_attention     SelfAttentionBlock's bmm / softmax / bmm   models/blocks.py:84-95             (_SelfAttentionFused | _SelfAttention)
 """
 from __future__ import annotations
 
@@ -727,6 +728,72 @@ class _SelfAttention(Function):
         return g, to4(dq, C8), to4(dk, C8), to4(dv, C), dgamma
 
 
+class _SelfAttentionFused(Function):
+    """The same function as _SelfAttention for N = H*W > 1 on the flash-style kernels (csrc/attention.hip): one launch forward for
+    the whole batch, at most five backward, and no (B, N, N) map: backward recomputes it from the per-row log-sum-exp.  Saves
+    q, k, v, o, lse and gamma (o because gamma may be 0, so it cannot be had from the output)."""
+
+    @staticmethod
+    def forward(ctx, x, q, k, v, gamma):
+        x, q, k, v = _cl(x), _cl(q), _cl(k), _cl(v)
+        B, C, H, W = x.shape
+        N, C8 = H * W, q.shape[1]
+        ctx.dims = (B, C, H, W, C8)
+        xm, qm, km, vm = (t.permute(0, 2, 3, 1).reshape(B, N, -1) for t in (x, q, k, v))      # views of the NHWC memory
+        gamma = gamma.detach().reshape(1).contiguous()
+        y, o, lse = ops.attention_fwd(qm, km, vm, xm, gamma)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(qm, km, vm, o, lse, gamma)
+        return y.view(B, H, W, C).permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        qm, km, vm, o, lse, gamma = ctx.saved_tensors
+        B, C, H, W, C8 = ctx.dims
+        need = ctx.needs_input_grad
+        g = _cl(g)
+        gm = g.permute(0, 2, 3, 1).reshape(B, H * W, C)
+        dq, dk, dv, dgamma = ops.attention_bwd(qm, km, vm, o, lse, gm, gamma, need[1], need[2], need[3])
+        to4 = lambda t, c: None if t is None else t.view(B, H, W, c).permute(0, 3, 1, 2)
+        return g if need[0] else None, to4(dq, C8), to4(dk, C8), to4(dv, C), dgamma if need[4] else None
+
+
+_ATTENTION_ROUTE = "auto"
+
+
+def set_attention_route(route: str) -> None:
+    """Which kernels run ``self_attention`` for N = H*W > 1: "fused" (the flash-style kernels, no N x N map), "gemm" (per image
+    three GEMMs and a row softmax, the map kept for backward) or "auto" (the default: attention_route_for).  Both are exact fp32;
+    ``set_conv_precision`` does not reach either.  N = 1 short-circuits on every route."""
+    global _ATTENTION_ROUTE
+    if route not in ("auto", "fused", "gemm"):
+        raise ValueError("attention route must be 'auto', 'fused' or 'gemm'")
+    _ATTENTION_ROUTE = route
+
+
+def get_attention_route() -> str:
+    return _ATTENTION_ROUTE
+
+
+def attention_route_for(B: int, N: int, dq: int, C: int) -> str:
+    """What "auto" resolves to, a pure host function of the shape: "gemm" at N = 1 (the short-circuit lives there), else the route
+    whose forward + backward is estimated faster by the two-term model fitted to the measured table of DESIGN.md section 11.2
+    (profiles/r12_attention.json; the model reproduces all nine measured shapes' winners):
+      fused  its workgroups walk N/64 swept tiles, each a chain of 32-column contraction steps at ~1.4 us per step: dK and dQ
+             (C/32 + dq/32 + 2 steps each) and forward and dV (dq/32 + 2 steps each); longer by B * N/64 / 512 once the
+             workgroups no longer fit the chip at once;
+      gemm   8 entry-point calls per image at ~11.6 us each, or 6 (C + dq) N^2 B flops at ~40 TF/s, whichever is larger.
+    So "fused" where the GEMM route is launch-bound (many images, short sweeps: RefineNet's (16, 258, 32, 256), 7x faster) and
+    "gemm" where few images do much work each (ValueEncoder's (4, 2048, 90, 720): the fused backward takes 2x the time there and
+    is chosen only by ``set_attention_route("fused")``, for its memory: no (B, N, N) map)."""
+    if N == 1:
+        return "gemm"
+    tiles, ns, nc = -(-N // 64), -(-dq // 32), -(-C // 32)
+    fused_us = 1.4 * tiles * (2 * (nc + ns + 2) + 2 * (ns + 2)) * max(1.0, B * tiles / 512.0)
+    gemm_us = max(11.6 * 8 * B, 6.0 * (C + dq) * N * N * B / 40e6)
+    return "fused" if fused_us <= gemm_us else "gemm"
+
+
 class _L1Mean(Function):
     @staticmethod
     def forward(ctx, a, b):
@@ -923,7 +990,15 @@ def softmax_rows(x2d):
 
 
 def self_attention(x, q, k, v, gamma):
-    return _SelfAttention.apply(x, q, k, v, gamma)
+    """SelfAttentionBlock's core on the already-projected maps: gamma * softmax(q k^T) v + x per image (models/blocks.py:77-96),
+    on the route ``set_attention_route`` names."""
+    B, C, H, W = x.shape
+    route = _ATTENTION_ROUTE
+    if route == "auto":
+        route = attention_route_for(B, H * W, q.shape[1], C)
+    if H * W == 1 or route == "gemm":
+        return _SelfAttention.apply(x, q, k, v, gamma)
+    return _SelfAttentionFused.apply(x, q, k, v, gamma)
 
 
 def cross_entropy(logits, labels):

@@ -586,6 +586,44 @@ def twin_head_bwd(h_adv, h_aux, w_adv, w_aux, adv, aux, d_adv, d_aux, out=None):
     return (dh_adv, dh_aux, *grads)
 
 
+def _attn_dims(q, k, v):
+    B, N, dq = q.shape
+    C = v.shape[2]
+    assert tuple(k.shape) == (B, N, dq) and tuple(v.shape) == (B, N, C) and all(t.is_contiguous() for t in (q, k, v))
+    return B, N, dq, C
+
+
+def attention_bwd_workspace_bytes(B: int, N: int, dq: int, C: int) -> int:
+    return int(_lib.load().vp_attn_bwd_workspace_bytes(B, N, dq, C))
+
+
+def attention_fwd(q, k, v, x, gamma):
+    """y = gamma * softmax(q k^T) v + x per image, one launch, no N x N map: contiguous q, k (B, N, dq), v, x (B, N, C), gamma (1,)
+    on the device.  Returns (y, o, lse): o = softmax(q k^T) v (B, N, C) and lse (B, N) are what attention_bwd needs."""
+    B, N, dq, C = _attn_dims(q, k, v)
+    assert x.shape == v.shape and x.is_contiguous() and gamma.numel() == 1
+    y, o = torch.empty_like(x), torch.empty_like(x)
+    lse = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    _lib.call("vp_attn_fwd_f32", _p(q), _p(k), _p(v), _p(x), _p(gamma), _p(y), _p(o), _p(lse), B, N, dq, C, _stream())
+    return y, o, lse
+
+
+def attention_bwd(q, k, v, o, lse, g, gamma, need_q: bool = True, need_k: bool = True, need_v: bool = True):
+    """Gradients of attention_fwd against the upstream gradient g (B, N, C): (dq, dk, dv, dgamma (1,)); a gradient that is not
+    needed is None and its kernel is not launched.  The attention map is recomputed from lse; dx is g itself."""
+    B, N, dq, C = _attn_dims(q, k, v)
+    assert o.shape == v.shape and g.shape == v.shape and o.is_contiguous() and g.is_contiguous()
+    assert tuple(lse.shape) == (B, N) and lse.is_contiguous() and gamma.numel() == 1
+    d_q = torch.empty_like(q) if need_q else None
+    d_k = torch.empty_like(k) if need_k else None
+    d_v = torch.empty_like(v) if need_v else None
+    dgamma = torch.empty(1, dtype=torch.float32, device=q.device)
+    wk = _ws(attention_bwd_workspace_bytes(B, N, dq, C), q)
+    _lib.call("vp_attn_bwd_f32", _p(q), _p(k), _p(v), _p(o), _p(lse), _p(g), _p(gamma), _p(d_q), _p(d_k), _p(d_v), _p(dgamma),
+              _p(wk), wk.numel() * 4, B, N, dq, C, _stream())
+    return d_q, d_k, d_v, dgamma
+
+
 def softmax_rows_fwd(x2d):
     R, n = x2d.shape
     y = torch.empty_like(x2d)

@@ -1,15 +1,21 @@
-"""GPU tests of the flash-style SelfAttentionBlock kernels (csrc/attention.hip) behind functional.self_attention: the case table of
-tests/attention_ref.py against fp64 on both routes, the masking, layout, reproducibility, launch-count and memory conditions, the
-block itself against the oracle, and the entry points' refusals."""
+"""GPU tests of the flash-style SelfAttentionBlock kernels (csrc/attention.hip) behind functional.self_attention: the case tables of
+tests/attention_ref.py (the random cases and the plan-branch cases) against fp64 on both routes, the structured energies that pin the
+online softmax, the masking, layout, reproducibility, launch-count and memory conditions, the block itself against the oracle, the
+entry points' refusals, guarded runs through the C ABI, unaligned bases, the batch at the grid's bound and the VP_ATTN_NT knob."""
 import ctypes
+import json
 import math
+import os
+import subprocess
+import sys
 
 import pytest
 import torch
 
 import vae_play_amd
 from tests import attention_ref as R
-from tests.util import assert_close
+from tests.guarded import Guards, same_bits
+from tests.util import ROOT, assert_close, record
 from vae_play_amd import _lib, functional, ops
 
 pytestmark = pytest.mark.gpu
@@ -68,7 +74,7 @@ def check(out, ref, what):
 
 
 @pytest.mark.parametrize("route", ["fused", "gemm"])
-@pytest.mark.parametrize("case", R.CASES, ids=R.case_id)
+@pytest.mark.parametrize("case", R.ALL_CASES, ids=R.case_id)
 def test_case_table_against_fp64(case, route):
     inp, ref = R.reference(case)
     check(run(inp, route), ref, route)
@@ -273,3 +279,126 @@ def test_abi_refusals_launch_nothing():
     _bwd(t, dims, null="dq")
     torch.cuda.synchronize()
     assert bool((t["dq"] == 7.0).all()) and not bool((t["dk"] == 7.0).any()) and not bool((t["y"] == 7.0).any())
+
+
+# ---- the fused kernels through ops / the C ABI: what functional.self_attention does not let through (N = 1) or does not show -------------
+OUTS = ("y", "o", "lse", "dq", "dk", "dv", "dgamma")
+
+
+def fused(t):
+    """ops.attention_fwd + attention_bwd on device operands: every output of the two entry points"""
+    y, o, lse = ops.attention_fwd(t["q"], t["k"], t["v"], t["x"], t["gamma"])
+    d_q, d_k, d_v, dgamma = ops.attention_bwd(t["q"], t["k"], t["v"], o, lse, t["g"], t["gamma"])
+    torch.cuda.synchronize()
+    return dict(zip(OUTS, (y, o, lse, d_q, d_k, d_v, dgamma)))
+
+
+def on_device(inp):
+    return {n: inp[n].to(DEV) for n in ("q", "k", "v", "x", "g", "gamma")}
+
+
+def held(ratios, what):
+    """every error / bound recorded and printed, then all of them finite and <= 1"""
+    for n, v in ratios.items():
+        record(f"{what} {n} / bound", v)
+    print(what, {n: f"{v:.3g}" for n, v in ratios.items()})
+    assert R.misses(ratios) == [], (what, ratios)
+
+
+@pytest.mark.parametrize("name", R.STRUCTURED)
+def test_structured_energies(name):
+    """Energies whose maximum moves where the case says (tests/attention_ref.py: up / down per key tile and per key, all far below
+    zero, one key): y, o, lse at Y_TOL, the gradients at GRAD_TOL times their fp64 conditioning.  tests/test_attention_cpu.py shows
+    which planted fault of the online softmax each one catches."""
+    inp, ref = R.structured_reference(name)
+    got = fused(on_device(inp))
+    for n in OUTS:
+        assert bool(torch.isfinite(got[n]).all()), n
+    held(R.structured_ratios(got, ref), f"structured {name}")
+    if name == "one":      # p = exp(0) = 1 for the one real key, 0 for the 63 phantom ones, l = 1: nothing rounds
+        assert torch.equal(got["o"].cpu(), inp["v"])
+
+
+@pytest.mark.parametrize("case", [R.BRANCH_CASES[0], R.BRANCH_CASES[6], R.BRANCH_CASES[4]], ids=R.case_id)
+def test_guarded_abi(case):
+    """vp_attn_fwd_f32 / vp_attn_bwd_f32 with every output between sentinels and a workspace of exactly the queried size: nothing
+    is stored past row N of the last image or past the workspace's partials, nothing is left unwritten, the values are the table's,
+    and a second call gives the same bits."""
+    assert R.BRANCH_CASES[0][:4] == (2, 66, 33, 65) and R.BRANCH_CASES[6][:4] == (33, 130, 4, 8) and R.BRANCH_CASES[4][:4] == (1, 65, 130, 16)
+    dims = B, N, dq, C = case[:4]
+    inp, ref = R.reference(case)
+    src = on_device(inp)
+
+    def once():
+        G = Guards(DEV)
+        t = dict(src, y=G.out("y", B, N, C), o=G.out("o", B, N, C), lse=G.out("lse", B, N), dq=G.out("dq", B, N, dq),
+                 dk=G.out("dk", B, N, dq), dv=G.out("dv", B, N, C), dgamma=G.out("dgamma", 1))
+        t["ws"], nbytes = G.ws("ws", int(_lib.load().vp_attn_bwd_workspace_bytes(*dims)))
+        assert nbytes == R.branches(case)["ws_bytes"] == t["ws"].numel() * 4
+        _fwd(t, dims)
+        _bwd(t, dims, ws_bytes=nbytes)
+        G.check()
+        return {n: t[n] for n in OUTS}
+
+    a, b = once(), once()
+    held(R.table_ratios(a, ref), "guarded")
+    for n in OUTS:
+        assert same_bits(a[n], b[n]), n
+
+
+def _one_float_in(t):
+    """a contiguous copy of t that starts 4 bytes into a larger allocation: not 16-byte aligned"""
+    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device=t.device)
+    v = buf[1:1 + t.numel()].view(t.shape)
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+@pytest.mark.parametrize("case", [R.CASES[6], R.BRANCH_CASES[2]], ids=R.case_id)
+def test_unaligned_bases_give_the_same_bits(case):
+    """dq % 4 == 0 and C % 4 == 0, so aligned bases take the 16-byte loads of load_run; with q, k, v, g starting one float into
+    their allocations the launchers must fall back to four 4-byte loads, which feed the same values into the same summation
+    order: every output equal bit for bit.  This checks the fall-back's arithmetic and that it is taken without a fault here; it
+    does not check that the hardware would refuse an unaligned 16-byte load."""
+    assert case[2] % 4 == 0 and case[3] % 4 == 0 and R.branches(case)["vec_s"] == R.branches(case)["vec_c"] == 1
+    src = on_device(R.reference(case)[0])
+    assert all(src[n].data_ptr() % 16 == 0 for n in ("q", "k", "v", "g"))
+    a = fused(src)
+    b = fused(dict(src, **{n: _one_float_in(src[n]) for n in ("q", "k", "v", "g")}))
+    for n in OUTS:
+        assert same_bits(a[n], b[n]), n
+    held(R.table_ratios(a, R.reference(case)[1]), "aligned")
+
+
+def test_batch_at_the_grid_bound():
+    """B = 65535 is the largest batch attn_check_dims lets through (the grid's z); test_abi_refusals_launch_nothing refuses 65536"""
+    case = (65535, 2, 1, 1, 1, 0)
+    inp, ref = R.reference(case)
+    got = fused(on_device(inp))
+    held(R.table_ratios(got, ref), "B = 65535")
+
+
+def test_attn_nt_knob():
+    """VP_ATTN_NT forces the channel chunk of forward / dV: chunks of 64 on C = 100, 129, 256, 720 (up to 12
+    chunks) and chunks of 128 on C = 8, 40, 64, plus the plan's own choice.  One fresh child process (the knob is read per launch
+    only with VP_ENV_DYNAMIC=1 set before the library loads) runs the fused kernels against fp64 and prints error / bound.
+    A column's arithmetic does not depend on the chunk it falls in, so the forced runs must also equal the plan's own bit for bit --
+    and a knob that was silently ignored would pass all of this: what is held is that either chunking of every C gives finite,
+    in-bound, identical results, not which one ran."""
+    env = dict(os.environ, VP_ENV_DYNAMIC="1")
+    env.pop("VP_ATTN_NT", None)
+    r = subprocess.run([sys.executable, "-m", "tests.attention_ref"], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    want = {"4": R.NT_CASES[4], "8": R.NT_CASES[8], "unset": R.NT_CASES[4] + R.NT_CASES[8]}
+    same = res.pop("same_bits")
+    assert sorted(res) == sorted(want)
+    assert sorted(same) == sorted(f"{k} {R.case_id(c)}" for k in ("4", "8") for c in R.NT_CASES[int(k)]) and all(same.values()), same
+    for knob, cases in want.items():
+        assert sorted(res[knob]) == sorted(R.case_id(c) for c in cases), knob
+        for cid, ratios in res[knob].items():
+            assert sorted(ratios) == sorted(OUTS)
+            held(ratios, f"VP_ATTN_NT {knob} {cid}")
